@@ -1,9 +1,14 @@
 #!/usr/bin/env python
 """Headline benchmark: IQ windows/sec of the DCLL LIF timestep loop (radio_ml_conv.yaml, 16x16 I/Q plane, T=128).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_per_gpu] [--plane R]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_per_gpu] [--plane R] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, runs W warm-up and K timed steps, writes the last timed step's outputs if `--dump-outputs` is given,
+and prints the line (headline, `ms_per_step`, the roofline from the HIP events of the timed launches).  `--full` adds
+every other measurement and check (upload-inclusive steps, live PMC traffic, CPU baseline, per-step paths, T = 1024,
+batch sweep, 128x128 plane, config 5, trained top-1); each has a switch of its own that an explicit value overrides.
 
 One step = one pass of the hot path over one batch of synthetic IQ windows already resident in HBM:
 net.zero_states() + net.reset() -> all T steps of all three layers (fused sequence kernels; the IQ -> spike encoding
@@ -12,8 +17,9 @@ That is the span of the reference's test_radio_ml.py:142-146 plus its input enco
 `--plane 128` runs the same path on the reference's argparse-default 128x128 I/Q plane (test_radio_ml.py:52; tiled
 kernels k_lif_seq_c1t / k_lif_seq_c32t, default batch 64) — a secondary configuration, not the headline number.
 Prints ONE JSON line on rank 0 (contract in the task statement) incl. `roofline` for the dominant kernel
-(k_lif_seq_c32d, fp32 MFMA bound; `traffic` = its HBM bytes per launch measured in the run by two `rocprofv3 --pmc` child
-passes) and `cpu_baseline` (the torch-CPU port of the reference timed on this host).
+(k_lif_seq_c32d, fp32 MFMA bound; `traffic` = its HBM bytes per launch — with --full measured in the run by two
+`rocprofv3 --pmc` child passes, else the committed summary under profiles/ when it is for this batch) and, with --full,
+`cpu_baseline` (the torch-CPU port of the reference timed on this host).
 """
 import argparse
 import json
@@ -175,7 +181,7 @@ def per_step_paths(dev, batch=512, steps=48, reps=3):
     return out
 
 
-def run_ref_network(dev, B, steps, warmup, rank=0, world=1, validate=True):
+def run_ref_network(dev, B, steps, warmup, rank=0, world=1, validate=True, dump=None):
     """BASELINE config 5 as this build defines it (quant.py; the reference has no quantisation code, so
     parity is unpinned): radio_ml_conv_ref.yaml — 7 x (64 channels, (1,3) kernels, (1,2) pooling) — on a Q=16 x I=128 I/Q
     plane, per-output-channel int8 conv weights handed to the kernels AS INT8 through the C ABI (dcll_layer_opts), 1-bit
@@ -221,7 +227,8 @@ def run_ref_network(dev, B, steps, warmup, rank=0, world=1, validate=True):
         if fused:
             res = net.test_sequence(iq=iq, encoder=enc, T=T_STEPS, t0=0, collect=False, profile=prof)
             last["res"] = res
-            return parallel.allreduce_tallies(parallel.tallies(res["vote"], labels, N_CLASSES))
+            last["tal"] = parallel.allreduce_tallies(parallel.tallies(res["vote"], labels, N_CLASSES))
+            return last["tal"]
         cells = enc(iq, T_STEPS, t0=0)
         planes = ops.cells_to_planes(cells, H * W)
         for t in range(T_STEPS):
@@ -248,6 +255,10 @@ def run_ref_network(dev, B, steps, warmup, rank=0, world=1, validate=True):
         tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
         parallel.all_reduce_(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if dump and rank == 0:
+        if "res" not in last:
+            raise SystemExit("--dump-outputs: the per-step path of this geometry keeps no outputs")
+        dump_outputs(dump, last["res"], last["tal"])
     # the timed outputs are checked (untimed): 16 windows spread over the batch, run again on a network of the same seeds at
     # batch 16 — every wave of a sample co-resident, the regime the oracle-checked tests cover — must give the same votes in
     # all seven layers and the same output logits.  (Round 5's first-layer kernel passed every small test and was wrong for
@@ -336,7 +347,8 @@ def bench_ref_network(a):
     assert world == a.gpus, "torchrun --nproc-per-node must equal --gpus (WORLD_SIZE=%d, --gpus %d)" % (world, a.gpus)
     dev = torch.device("cuda", parallel.local_device(local_rank))
     torch.cuda.set_device(dev)
-    rec = run_ref_network(dev, a.batch or 1024, a.steps, a.warmup, rank, world, validate=bool(a.validate))
+    rec = run_ref_network(dev, a.batch or 1024, a.steps, a.warmup, rank, world, validate=bool(a.validate),
+                          dump=a.dump_outputs)
     if parallel.is_distributed():
         parallel.barrier()
     if rank == 0:
@@ -501,6 +513,43 @@ def live_hbm_traffic(extra_args, kernel_prefix, timeout=300):
                  (vals["FETCH_SIZE"][1], vals["WRITE_SIZE"][1], kernel_prefix))
 
 
+DUMP_LIMIT_BYTES = 60 * 2 ** 20          # (below 64 MB however counted)
+DUMP_SAMPLE_SEED, DUMP_SAMPLE_MAX = 20240, 512
+
+
+def dump_outputs(out_dir, res, tal):
+    """`--dump-outputs DIR`: what the last timed step handed its caller, as DIR/<name>.npy — per layer i the votes of every
+    window (vote_layer{i}, (B)), and for a fixed seeded sample of windows (sample_windows, their batch positions) the
+    per-step argmax (clout_layer{i}, (T,S)) and logits (logits_layer{i}, (T,S,24); output_logits = the output_ layer's);
+    the all-reduced tallies (tallies, (L, 24*24 + 2)).  Integers go out as float32 (votes, argmax) or float64 (tallies),
+    exactly.  The sample is sized so that everything stays under DUMP_LIMIT_BYTES."""
+    os.makedirs(out_dir, exist_ok=True)
+    votes = [v for v in res["vote"] if v is not None]
+    per_step = [x for x in res["logits"] + res["clout"] if x is not None] + ([res["o"]] if res.get("o") is not None else [])
+    T, B = per_step[0].shape[:2]
+    window_bytes = sum(4 * T * (x.shape[2] if x.dim() == 3 else 1) for x in per_step)
+    room = DUMP_LIMIT_BYTES - 4 * B * len(votes) - 8 * tal.numel() - 4 * DUMP_SAMPLE_MAX - 2 ** 16      # (+ .npy headers)
+    S = max(1, min(B, DUMP_SAMPLE_MAX, room // window_bytes))
+    pick = np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).choice(B, S, replace=False))
+    idx = torch.from_numpy(pick).to(per_step[0].device)
+    arrays = {"tallies": tal.cpu().numpy().astype(np.float64), "sample_windows": pick.astype(np.float32)}
+    for i, x in enumerate(res["vote"]):
+        if x is not None:
+            arrays["vote_layer%d" % i] = x.cpu().numpy().astype(np.float32)
+    for key, name in (("clout", "clout_layer%d"), ("logits", "logits_layer%d")):
+        for i, x in enumerate(res[key]):
+            if x is not None:
+                arrays[name % i] = x.index_select(1, idx).cpu().numpy().astype(np.float32)
+    if res.get("o") is not None:
+        arrays["output_logits"] = res["o"].index_select(1, idx).cpu().numpy().astype(np.float32)
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, total
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    log("outputs of the last timed step: %d arrays, %.1f MB (%d of %d windows per step-wise array) -> %s" % (
+        len(arrays), total / 2 ** 20, S, B, out_dir))
+
+
 def log(msg):
     print("[bench %7.1fs] %s" % (time.perf_counter() - _T0, msg), file=sys.stderr, flush=True)
 
@@ -588,42 +637,55 @@ def main():
     ap.add_argument("--steps-T", type=int, default=128, dest="steps_T",
                     help="timesteps per window T (IQ windows of max(128, T) samples).  128 = BASELINE's metric; 1024 = the "
                          "reference's n_iters default and script setting (train.py:63-66, scripts/test_radio_ml.sh:17-18)")
-    ap.add_argument("--t1024", type=int, default=1,
-                    help="1 (default, N=1 headline run only): also run T = 1024 at batch 512 (2 steps) and report it as `t1024`")
-    ap.add_argument("--batch-sweep", type=int, default=1,
-                    help="1 (default, N=1 headline run only): also run BASELINE configs 2 and 3 (batch 512 and 8192, 3 steps "
-                         "each) and report them as `batch_sweep`")
-    ap.add_argument("--live-traffic", type=int, default=1,
-                    help="1 (default, N=1 only): measure roofline.traffic in this run — two child passes of this command under "
-                         "rocprofv3 --pmc (FETCH_SIZE, WRITE_SIZE; ~30 s); 0 or on failure: the committed builder-side summary")
-    ap.add_argument("--trained", type=int, default=1,
-                    help="1 (default, N=1 headline run only): also train the network on the synthetic modulation set (train.py, "
-                         "25 batches of 512) and compare top-1 of the fused path with the CPU reference path on 2048 held-out "
-                         "windows: `trained_top1`")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: the upload-inclusive steps, live PMC "
+                         "traffic, CPU baseline, per-step paths, T = 1024, batch sweep, 128x128 plane, config 5, trained top-1 "
+                         "(each switch below defaults to 1 with --full and to 0 without; an explicit value wins)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, "
+                         "< 64 MB): per layer the votes of every window, the per-step argmax and the logits of a fixed seeded "
+                         "sample of windows, and the tallies")
+    ap.add_argument("--t1024", type=int, default=None,
+                    help="1 (default with --full, N=1 headline run only): also run T = 1024 at batch 512 (2 steps) and report it "
+                         "as `t1024`")
+    ap.add_argument("--batch-sweep", type=int, default=None,
+                    help="1 (default with --full, N=1 headline run only): also run BASELINE configs 2 and 3 (batch 512 and 8192, "
+                         "3 steps each) and report them as `batch_sweep`")
+    ap.add_argument("--live-traffic", type=int, default=None,
+                    help="1 (default with --full, N=1 only): measure roofline.traffic in this run — two child passes of this "
+                         "command under rocprofv3 --pmc (FETCH_SIZE, WRITE_SIZE; ~30 s); 0 or on failure: the committed "
+                         "builder-side summary")
+    ap.add_argument("--trained", type=int, default=None,
+                    help="1 (default with --full, N=1 headline run only): also train the network on the synthetic modulation set "
+                         "(train.py, 25 batches of 512) and compare top-1 of the fused path with the CPU reference path on 2048 "
+                         "held-out windows: `trained_top1`")
     ap.add_argument("--cpu-windows", type=int, default=None,
-                    help="CPU baseline batch (0 = skip); default 512 = batch_size_test of the reference's scripts "
-                         "(4 on planes larger than 16x16, where the CPU path needs seconds per window)")
+                    help="CPU baseline batch (0 = skip); default without --full 0, with --full 512 = batch_size_test of the "
+                         "reference's scripts (4 on planes larger than 16x16, where the CPU path needs seconds per window)")
     ap.add_argument("--fuse-readout", type=int, default=0, help="1: readouts in the layer kernel's epilogue")
     ap.add_argument("--output-only", type=int, default=0,
                     help="1: serving mode — hidden layers skip pv and their local readouts (NOT the headline workload)")
     ap.add_argument("--overlap-readout", type=int, default=None,
                     help="1: readouts / statistics / votes on a second stream under the next layer's kernel "
                          "(default: DCLL_OVERLAP_READOUT)")
-    ap.add_argument("--per-step", type=int, default=1,
-                    help="1 (default, N=1 only): also time the per-timestep protocol net.test / net.learn at batch 512 and "
-                         "report it as `per_step_paths` (a second or two; not part of `value`)")
-    ap.add_argument("--config5", type=int, default=1,
-                    help="1 (default, N=1 headline run only): also run BASELINE config 5 (radio_ml_conv_ref.yaml, int8 weights "
-                         "through the ABI, batch 4096, 3 steps) and report it as the `config5` sub-record")
-    ap.add_argument("--plane128", type=int, default=1,
-                    help="1 (default, N=1 headline run only): also run the reference's argparse-default 128x128 plane at batch 64 "
-                         "(2 steps + 4 windows of the CPU path) and report it as the `plane128` sub-record")
-    ap.add_argument("--validate", type=int, default=1,
-                    help="1 (default): config 5 re-runs 16 windows of its timed batch at batch 16 and compares (0: the PMC child "
-                         "passes — their per-launch averages must see the timed launches only)")
+    ap.add_argument("--per-step", type=int, default=None,
+                    help="1 (default with --full, N=1 only): also time the per-timestep protocol net.test / net.learn at batch "
+                         "512 and report it as `per_step_paths` (a second or two; not part of `value`)")
+    ap.add_argument("--config5", type=int, default=None,
+                    help="1 (default with --full, N=1 headline run only): also run BASELINE config 5 (radio_ml_conv_ref.yaml, "
+                         "int8 weights through the ABI, batch 4096, 3 steps) and report it as the `config5` sub-record")
+    ap.add_argument("--plane128", type=int, default=None,
+                    help="1 (default with --full, N=1 headline run only): also run the reference's argparse-default 128x128 "
+                         "plane at batch 64 (2 steps + 4 windows of the CPU path) and report it as the `plane128` sub-record")
+    ap.add_argument("--validate", type=int, default=None,
+                    help="1 (default with --full): `--network ref` re-runs 16 windows of its timed batch at batch 16 and "
+                         "compares (0: the PMC child passes — their per-launch averages must see the timed launches only)")
     ap.add_argument("--network", default="radio", choices=["radio", "ref"],
                     help="radio = radio_ml_conv.yaml (headline); ref = radio_ml_conv_ref.yaml with int8 weights (config 5)")
     a = ap.parse_args()
+    for name in ("t1024", "batch_sweep", "live_traffic", "trained", "per_step", "config5", "plane128", "validate"):
+        if getattr(a, name) is None:
+            setattr(a, name, int(a.full))
     if a.gpus > 1 and not parallel.under_launcher():
         # started plainly (`python bench.py --gpus N`): this process becomes the launcher of N fresh rank processes and
         # never touches the GPU itself; rank 0's JSON line goes straight to our stdout.  Under torchrun the ranks
@@ -637,7 +699,7 @@ def main():
     if a.batch is None:
         a.batch = 4096 if R == 16 else 64
     if a.cpu_windows is None:
-        a.cpu_windows = 512 if R == 16 else 4
+        a.cpu_windows = (512 if R == 16 else 4) if a.full else 0
     hot_kernel = "k_lif_seq_c32d" if R == 16 else "k_lif_seq_c32t"
 
     rank, local_rank, world = parallel.init_process_group()
@@ -713,22 +775,26 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     log("timed region done: %.3f s for %d steps" % (dt, a.steps))
-    # the same K steps with the raw IQ handed over as a HOST buffer each step ("with and without
-    # encode+upload", reference test_radio_ml.py:133-135 — there a dense T*B*R*R fp32 spike tensor, here 1 KB of raw IQ per
-    # window from pinned memory; the encoding runs inside the first layer's kernel either way).  Never `value`.
-    iq_host = iq.cpu().pin_memory()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, res, tal)
+    dt_up = None
+    if a.full:
+        # the same K steps with the raw IQ handed over as a HOST buffer each step ("with and without
+        # encode+upload", reference test_radio_ml.py:133-135 — there a dense T*B*R*R fp32 spike tensor, here 1 KB of raw IQ
+        # per window from pinned memory; the encoding runs inside the first layer's kernel either way).  Never `value`.
+        iq_host = iq.cpu().pin_memory()
 
-    def step_upload():
-        iq.copy_(iq_host, non_blocking=True)
-        return step()
+        def step_upload():
+            iq.copy_(iq_host, non_blocking=True)
+            return step()
 
-    step_upload()
-    fence()
-    t0 = time.perf_counter()
-    for _ in range(a.steps):
         step_upload()
-    fence()
-    dt_up = time.perf_counter() - t0
+        fence()
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            step_upload()
+        fence()
+        dt_up = time.perf_counter() - t0
     multi = None
     if parallel.is_distributed():
         # max over ranks = the job's time (contract); min / max of the ranks' own clocks, of the device time of their layer
@@ -736,9 +802,13 @@ def main():
         # collective (allreduce_ms_per_step), or the host (wall >> device_busy on every rank)
         ar_ms = float(np.sum([s_.elapsed_time(e_) for s_, e_ in prof.get("allreduce", [])])) / max(1, a.steps)
         busy_ms = float(np.sum([s_.elapsed_time(e_) for k_, v_ in prof.items() if k_ != "allreduce" for s_, e_ in v_])) / max(1, a.steps)
-        dt, dt_up, multi = parallel.job_timing(dt, dt_up, ar_ms, busy_ms, a.steps, dev, "%s/cuda:%d/%s" % (
-            os.uname().nodename, dev.index, parallel.device_identity(dev.index)))
-    log("upload-inclusive region done: %.3f s for %d steps" % (dt_up, a.steps))
+        dt, dt_up_max, multi = parallel.job_timing(dt, 0.0 if dt_up is None else dt_up, ar_ms, busy_ms, a.steps, dev,
+                                                   "%s/cuda:%d/%s" % (os.uname().nodename, dev.index,
+                                                                      parallel.device_identity(dev.index)))
+        if dt_up is not None:
+            dt_up = dt_up_max
+    if dt_up is not None:
+        log("upload-inclusive region done: %.3f s for %d steps" % (dt_up, a.steps))
 
     # dominant kernel: HIP-event time of every k_lif_seq_c32d launch of the timed region (same stream as the launch)
     c32_ms = [s.elapsed_time(e) for s, e in prof.get("lif_c32", [])]
@@ -822,11 +892,12 @@ def main():
             # the all-reduced tallies of the last step: (correct, total) per layer and a digest of the confusion matrices
             "tallies": {"correct_total": [[int(v) for v in row] for row in tal[:, -2:].cpu()],
                         "confusion_sha1": __import__("hashlib").sha1(cm.cpu().numpy().astype(np.int64).tobytes()).hexdigest()},
-            "value_incl_upload": total_windows * a.steps / dt_up,
-            "ms_per_step_incl_upload": 1e3 * dt_up / a.steps,
-            "upload": "raw IQ (B,2,%d) fp32 = %d bytes per step per GPU, pinned host memory -> HBM on the launch stream, in "
-                      "front of every step; `value` is the device-resident form" % (L_IQ, B * 2 * L_IQ * 4),
         }
+        if dt_up is not None:
+            out["value_incl_upload"] = total_windows * a.steps / dt_up
+            out["ms_per_step_incl_upload"] = 1e3 * dt_up / a.steps
+            out["upload"] = ("raw IQ (B,2,%d) fp32 = %d bytes per step per GPU, pinned host memory -> HBM on the launch stream, "
+                             "in front of every step; `value` is the device-resident form" % (L_IQ, B * 2 * L_IQ * 4))
         # the HBM-bound kernels around the hot one (north_star: achieved HBM GB/s of the LIF-update kernel against the
         # roofline): bytes they must move by this design (pv written once by the first layer's kernel, read once by a
         # readout GEMM; + packed spikes / logits), over their HIP-event time of this run

@@ -120,7 +120,7 @@ def test_bench_strong_scaling_flag_fixes_the_global_batch():
     lines = {}
     for n in (1, 4):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "1", "--warmup", "1",
-                            "--global-batch", "1027", "--cpu-windows", "0", "--per-step", "0", "--config5", "0",
+                            "--global-batch", "1027", "--full", "--cpu-windows", "0", "--per-step", "0", "--config5", "0",
                             "--live-traffic", "0", "--batch-sweep", "0", "--plane128", "0", "--trained", "0", "--t1024", "0"],
                            env=env, capture_output=True, text=True, timeout=1000)
         assert r.returncode == 0, r.stderr[-3000:]
