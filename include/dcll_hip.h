@@ -54,7 +54,10 @@ typedef struct dcll_conv_desc {
                                        * Other values (>= 1, groups dividing c_in and c_out; W is then (c_out, c_in/groups,
                                        * kh, kw), the chain runs over the group's channel pairs) are served by the per-step
                                        * calls dcll_conv_lif_step / dcll_conv_lif_backward[_open] on their generic kernels;
-                                       * the sequence calls return DCLL_ERR_UNSUPPORTED for them                          */
+                                       * the sequence calls return DCLL_ERR_UNSUPPORTED for them.  The backward calls serve
+                                       * kernels of up to 64 taps (kh * kw <= 64) whose padded input row fits the LDS-staged
+                                       * weight gradient (about (w + 2 pad_w) * ((kh - 1) dilation + 1) <= 12 000 floats) and
+                                       * return DCLL_ERR_UNSUPPORTED beyond — F.conv2d itself has no such limit            */
     int32_t pool_h, pool_w;     /* MaxPool2d(kernel=stride=pool, padding=(pool-1)/2)   :542-549          */
     int32_t target;             /* target_size: rows of i2o.weight (and output_.weight)                  */
     int32_t output_layer;       /* !=0: also o = output_(flatten(pv))  :605-606                          */
@@ -160,8 +163,8 @@ int dcll_conv_lif_step(const dcll_conv_desc *d, const float *x, const float *W, 
  *   the bits the kernel would recompute from v (what torch's sigmoid backward does, too) — and the step need not write out_v
  *   incoming gradients (each may be NULL): g_p (B,target) of pvoutput, g_o (B,target) of the output_ logits,
  *   g_pv (B,c_out,ph,pw) of pv, g_v (B,c_out,ch,cw) of pvmem
- *   results: dW (c_out,c_in,kh,kw), db (c_out) [may be NULL]; d_outW (target, c_out*ph*pw), d_outb (target) iff g_o
- *   scratch: scratch_floats >= B*c_out*ch*cw + k*c_out*(c_in*kh*kw + 1) floats with k >= 1 batch chunks for the weight
+ *   results: dW (c_out,c_in/groups,kh,kw), db (c_out) [may be NULL]; d_outW (target, c_out*ph*pw), d_outb (target) iff g_o
+ *   scratch: scratch_floats >= B*c_out*ch*cw + k*c_out*((c_in/groups)*kh*kw + 1) floats with k >= 1 batch chunks for the weight
  *   gradient's partial sums (more chunks = more parallelism; up to 256 are used).  An output_ layer with target <= 32 whose
  *   K = c_out*ph*pw is not a multiple of 32 sums its gradient over min(B, 16, m) batch chunks of target*(K+1) floats, m = what
  *   fits into the partial-sum area (closed form: the area is reused) or behind the rows in use (dcll_conv_lif_backward_open):
@@ -215,7 +218,7 @@ int dcll_adam_step_dyn(const dcll_adam_tensor *tensors, int32_t n_tensors, const
 /*
  * The end of a learning timestep in one launch (ABI 5).  dcll_conv_lif_backward_open is dcll_conv_lif_backward with the last
  * step of the weight gradient left open: the partial rows stay in `scratch` — *part points at *nchunk rows of
- * c_out * (c_in*kh*kw + 1) floats, valid until the next call that uses this scratch — and dW / db are not written.
+ * c_out * ((c_in/groups)*kh*kw + 1) floats, valid until the next call that uses this scratch — and dW / db are not written.
  * dcll_grad_reduce_adam then finishes up to DCLL_REDUCE_MAX_LAYERS layers at once: the rows are added in dcll_conv_lif_backward's
  * own fixed order (bit-identical gradients), written to dW / db, and the Adam update of `tensors[adam_w]` / `tensors[adam_b]`
  * (index, or -1: no update) is applied by the thread that holds the finished gradient element; the tensors no layer refers
@@ -225,8 +228,8 @@ int dcll_adam_step_dyn(const dcll_adam_tensor *tensors, int32_t n_tensors, const
 #define DCLL_REDUCE_MAX_LAYERS 4
 typedef struct dcll_grad_parts {
     const float *part;          /* nchunk partial rows (dcll_conv_lif_backward_open)                       */
-    float *dW, *db;             /* (c_out, c_in*kh*kw) and (c_out): the reduced gradients; db may be NULL  */
-    int64_t rowlen;             /* c_in*kh*kw + 1                                                          */
+    float *dW, *db;             /* (c_out, (c_in/groups)*kh*kw) and (c_out): the reduced gradients; db may be NULL */
+    int64_t rowlen;             /* (c_in/groups)*kh*kw + 1                                                 */
     int32_t nchunk, c_out;
     int32_t adam_w, adam_b;     /* entries of `tensors` to update with dW / db, or -1                      */
 } dcll_grad_parts;

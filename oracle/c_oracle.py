@@ -107,7 +107,7 @@ class OracleConvLayer:
 class OracleDenseLayer:
     def __init__(self, sd, wrp, alpharp=.65):
         f = lambda k: np.ascontiguousarray(np.asarray(sd[k], dtype=np.float32))
-        self.W, self.b = f("i2h.weight"), f("i2h.bias")
+        self.W, self.b = f("i2h.weight"), (f("i2h.bias") if "i2h.bias" in sd else None)      # (bias=False: chains start at 0)
         self.tau = [f("i2h.alpha"), f("i2h.tau_m__dt"), f("i2h.alphas"), f("i2h.tau_s__dt")]
         self.i2o_W, self.i2o_b = f("i2o.weight"), f("i2o.bias")
         self.d = DenseDesc(self.W.shape[1], self.W.shape[0], self.i2o_W.shape[0], int(self.tau[0].size > 1),

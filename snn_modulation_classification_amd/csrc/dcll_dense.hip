@@ -200,7 +200,7 @@ int dcll_launch_dense_mfma(const dcll_dense_desc *d, const float *eps1, const fl
     if (d->refractory) { if (narrow) DCLL_DENSE(true, 1); else DCLL_DENSE(true, 2); }
     else { if (narrow) DCLL_DENSE(false, 1); else DCLL_DENSE(false, 2); }
 #undef DCLL_DENSE
-    HIP_CHECK_LAUNCH("k_dense_lif_mfma");
+    HIP_CHECK_LAUNCH(narrow ? "k_dense_lif_mfma (narrow)" : "k_dense_lif_mfma (wide)");
     return DCLL_OK;
 }
 

@@ -2036,13 +2036,16 @@ static int launch_readout(const float *pv, const float *Wt, const float *bias, f
     if (direct_ok && mode == DCLL_READOUT_CORESIDENT)
         return dcll_launch_readout_direct(pv, Wt, bias, out, rows, K, N, st);
     if (fast && mode == DCLL_READOUT_T16) return dcll_launch_readout_t16(pv, Wt, bias, out, rows, K, N, 0, st);     // any row count
+    const char *form = "k_readout";
     if (rows <= 2048) {
+        form = "k_readout_rows";
         hipLaunchKernelGGL(k_readout_rows, dim3((unsigned)((rows + RS_RB - 1) / RS_RB), (N + RS_NG - 1) / RS_NG), dim3(256),
                            0, st, pv, Wt, bias, out, rows, K, N);
     } else if (fast && K % RK_KC == 0 && K >= 65536 && rows < 256L * RO_ROWS) {
         // long rows (large planes) and fewer 128-row tiles than CUs: 32-row tiles with the K-chunk split over the
         // waves.  (K of the 16x16 plane, 8192, always takes k_readout_v4: its logits then do not depend on how a
         // run is split into launches.)
+        form = "k_readout_ks";
         if (N <= 32)
             hipLaunchKernelGGL(k_readout_ks<1>, dim3(nblk(rows, RK_ROWS)), dim3(256), 0, st, pv, Wt, bias, out, rows, K, N, 0);
         else
@@ -2052,14 +2055,16 @@ static int launch_readout(const float *pv, const float *Wt, const float *bias, f
         // for the 32-column tiles of k_readout_v4 below, which stay for DCLL_READOUT_LDS)
         return dcll_launch_readout_t16(pv, Wt, bias, out, rows, K, N, 0, st);
     } else if (fast && N <= 32) {
+        form = "k_readout_v4";
         hipLaunchKernelGGL(k_readout_v4<1>, dim3(nblk(rows, RO_ROWS)), dim3(256), 0, st, pv, Wt, bias, out, rows, K, N);
     } else if (fast) {
+        form = "k_readout_v4";
         hipLaunchKernelGGL(k_readout_v4<2>, dim3(nblk(rows, RO_ROWS)), dim3(256), 0, st, pv, Wt, bias, out, rows, K, N);
     } else {
         dim3 grid(nblk(rows, RO_ROWS), (N + 31) / 32);
         hipLaunchKernelGGL(k_readout, grid, dim3(256), 0, st, pv, Wt, bias, out, rows, K, N);
     }
-    HIP_CHECK_LAUNCH("k_readout");
+    HIP_CHECK_LAUNCH(form);        // (the launch log names the form: k_readout = the plain kernel for any K / N / alignment)
     return DCLL_OK;
 }
 
@@ -2888,16 +2893,17 @@ extern "C" int dcll_conv_lif_step(const dcll_conv_desc *d, const float *x, const
 #define DCLL_TILED(KH_, KW_)                                                                                          \
     hipLaunchKernelGGL((k_conv_lif_tiled<KH_, KW_, COG>), tg, dim3(256), 0, st, *d, ch, cw, eps1, W, b, arp, s_full,    \
                        pv_full, out_v)
-        if (tile_ok && d->kh == 7 && d->kw == 7) DCLL_TILED(7, 7);
-        else if (tile_ok && d->kh == 5 && d->kw == 5) DCLL_TILED(5, 5);
-        else if (tile_ok && d->kh == 3 && d->kw == 3) DCLL_TILED(3, 3);
-        else if (tile_ok && d->kh == 1 && d->kw == 3) DCLL_TILED(1, 3);       // radio_ml_conv_ref.yaml
+        const char *form = "k_conv_lif";
+        if (tile_ok && d->kh == 7 && d->kw == 7) { DCLL_TILED(7, 7); form = "k_conv_lif_tiled<7,7>"; }
+        else if (tile_ok && d->kh == 5 && d->kw == 5) { DCLL_TILED(5, 5); form = "k_conv_lif_tiled<5,5>"; }
+        else if (tile_ok && d->kh == 3 && d->kw == 3) { DCLL_TILED(3, 3); form = "k_conv_lif_tiled<3,3>"; }
+        else if (tile_ok && d->kh == 1 && d->kw == 3) { DCLL_TILED(1, 3); form = "k_conv_lif_tiled<1,3>"; }      // radio_ml_conv_ref.yaml
         else
             hipLaunchKernelGGL(k_conv_lif, dim3(nblk(nconv, 256)), dim3(256), 0, st, *d, ch, cw, eps1, W, b, arp, s_full,
                                pv_full, out_v, nconv);
 #undef DCLL_TILED
+        HIP_CHECK_LAUNCH(form);
     }
-    HIP_CHECK_LAUNCH("k_conv_lif");
     if (pooled) {
         hipLaunchKernelGGL(k_pool, dim3(nblk(npool, 256)), dim3(256), 0, st, *d, ch, cw, ph, pw, s_full, pv_full, out_s,
                            out_pv, npool);
@@ -3119,12 +3125,13 @@ static int conv_lif_backward_impl(const dcll_conv_desc *d, const float *eps1, co
         return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward: v may be NULL only for a layer without pooling whose pv is given");
     if (g_p && !i2o_W) return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward: g_p needs i2o_W");
     if (g_o && (!pv_pooled || !d_outW || !d_outb)) return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward: g_o needs pv_pooled, d_outW, d_outb");
-    if (d->kh * d->kw > WG_MAXTAPS) return fail(DCLL_ERR_UNSUPPORTED, "dcll_conv_lif_backward: kernels up to 64 taps");
+    if (d->kh * d->kw > WG_MAXTAPS) return fail(DCLL_ERR_UNSUPPORTED, "dcll_conv_lif_backward: kernels up to 64 taps (kh * kw <= 64)");
     if (B < 1) return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward: empty batch");
     hipStream_t st = (hipStream_t)stream;
     int ch, cw, ph, pw;
     conv_shape(d, &ch, &cw, &ph, &pw);
     const long nconv = (long)B * d->c_out * ch * cw;
+    const char *dv_form = "k_bwd_dv";        // (the generic kernel: pooling, or more than 32 readout rows)
     if (dv_done) {
         // (dcll_conv_lif_backward_open_multi ran this layer's dv with the other layers': the gradient map is in scratch)
     } else if (nopool) {
@@ -3139,22 +3146,22 @@ static int conv_lif_backward_impl(const dcll_conv_desc *d, const float *eps1, co
             hipLaunchKernelGGL((k_bwd_dv_nopool<NP_, true>), grid, dim3(256), 0, st, Kmap, d->target, pv_pooled, g_p, g_pv, \
                                g_v, i2o_W, scratch, B, per_block);                                                      \
     } while (0)
-        if (d->target <= 8) DCLL_DV(8);
-        else if (d->target <= 16) DCLL_DV(16);
-        else if (d->target <= 24) DCLL_DV(24);
-        else DCLL_DV(32);
+        if (d->target <= 8) { DCLL_DV(8); dv_form = v ? "k_bwd_dv_nopool<8>" : "k_bwd_dv_nopool<8> (from pv)"; }
+        else if (d->target <= 16) { DCLL_DV(16); dv_form = v ? "k_bwd_dv_nopool<16>" : "k_bwd_dv_nopool<16> (from pv)"; }
+        else if (d->target <= 24) { DCLL_DV(24); dv_form = v ? "k_bwd_dv_nopool<24>" : "k_bwd_dv_nopool<24> (from pv)"; }
+        else { DCLL_DV(32); dv_form = v ? "k_bwd_dv_nopool<32>" : "k_bwd_dv_nopool<32> (from pv)"; }
 #undef DCLL_DV
     } else {
         hipLaunchKernelGGL(k_bwd_dv, dim3(nblk(nconv, 256)), dim3(256), 0, st, *d, ch, cw, ph, pw, v, g_p, g_pv, g_v, i2o_W,
                            scratch, nconv);
     }
-    if (!dv_done) HIP_CHECK_LAUNCH("k_bwd_dv");
+    if (!dv_done) HIP_CHECK_LAUNCH(dv_form);
     // weight gradient: partial sums over batch chunks (after the g_v_full plane in scratch), then a fixed-order reduce
     const long rowlen = (long)(d->c_in / d->groups) * d->kh * d->kw + 1;      // (a weight row: the c_in / groups channels of co's group)
     const long per_chunk = (long)d->c_out * rowlen;
     float *part = scratch + nconv;
     long nchunk = (scratch_floats - nconv) / per_chunk;
-    if (nchunk < 1) return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward: scratch too small (need B*c_out*ch*cw + k*(c_out*(c_in*kh*kw+1)), k >= 1)");
+    if (nchunk < 1) return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward: scratch too small (need B*c_out*ch*cw + k*(c_out*((c_in/groups)*kh*kw+1)), k >= 1)");
     const bool c32 = d->c_in == 32 && d->c_out == 32 && d->kh == 7 && d->kw == 7 && d->pad_h == 3 && d->pad_w == 3 && plain_conv(d);
     if (c32 && d->h == 16 && d->w == 16) {
         if (nchunk > 256) nchunk = 256;
@@ -3214,7 +3221,7 @@ static int conv_lif_backward_impl(const dcll_conv_desc *d, const float *eps1, co
         if (nchunk > B) nchunk = B;
         hipLaunchKernelGGL(k_bwd_wgrad, dim3(d->c_out * (d->c_in / d->groups), (unsigned)nchunk), dim3(256), lds, st, *d, ch, cw,
                            scratch, eps1, part, B, RB);
-        HIP_CHECK_LAUNCH("k_bwd_wgrad");
+        HIP_CHECK_LAUNCH(RB < ch ? "k_bwd_wgrad (row bands)" : "k_bwd_wgrad");
     }
     if (open_part) {
         *open_part = part;
@@ -3226,7 +3233,7 @@ static int conv_lif_backward_impl(const dcll_conv_desc *d, const float *eps1, co
             hipLaunchKernelGGL(k_bwd_reduce4<4>, dim3(nblk(per_chunk, 64)), dim3(256), 0, st, part, dW, db, (int)nchunk, d->c_out, rowlen);
         else
             hipLaunchKernelGGL(k_bwd_reduce, dim3(nblk(per_chunk, 256)), dim3(256), 0, st, part, dW, db, (int)nchunk, d->c_out, rowlen);
-        HIP_CHECK_LAUNCH("k_bwd_reduce");
+        HIP_CHECK_LAUNCH(nchunk >= 64 ? "k_bwd_reduce4<16>" : nchunk >= 16 ? "k_bwd_reduce4<4>" : "k_bwd_reduce");
     }
     if (g_o) {
         const int K = d->c_out * ph * pw, N = d->target;

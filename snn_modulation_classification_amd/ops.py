@@ -38,7 +38,7 @@ def conv_lif_backward_open_multi(deferred):
     check(_lib.get().dcll_conv_lif_backward_open_multi(arr, len(deferred), stream_ptr()), "dcll_conv_lif_backward_open_multi")
     for e, a in zip(deferred, arr):
         d = e['desc']
-        e['out']['parts'] = dict(part=a.part, nchunk=a.nchunk, c_out=d.c_out, rowlen=d.c_in * d.kh * d.kw + 1, dW=e['dW'],
+        e['out']['parts'] = dict(part=a.part, nchunk=a.nchunk, c_out=d.c_out, rowlen=(d.c_in // d.groups) * d.kh * d.kw + 1, dW=e['dW'],
                                  db=e['db'], keep=e['scratch'])
 
 
@@ -244,8 +244,11 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
     if scratch is None or scratch.numel() != n_scratch:
         scratch = out['bwd_scratch'] = torch.empty((n_scratch,), device=dev, dtype=torch.float32)
     c = lambda t: None if t is None else _f32(t, "grad").contiguous()
+    # the contiguous copies are bound to locals until the call is enqueued: a temporary's block goes back to the caching
+    # allocator as soon as ptr() returns, and the NEXT temporary's copy can be given the same block (two expanded stride-0
+    # gradients in one call would then alias)
+    gp_, go_, gpv_, gv_ = c(g_p), (c(g_o) if want_out else None), c(g_pv), c(g_v)
     if defer is not None:       # (open form, launched later with other layers': conv_lif_backward_open_multi)
-        gp_, go_, gpv_, gv_ = c(g_p), (c(g_o) if want_out else None), c(g_pv), c(g_v)
         item = _lib.BwdItem(ctypes.pointer(desc), ptr(eps1), ptr(v), ptr(pv_pooled), ptr(gp_), ptr(go_), ptr(gpv_), ptr(gv_),
                             ptr(i2o_W), ptr(d_outW), ptr(d_outb), ptr(scratch), n_scratch, B, 0, None, 0, 0)
         defer.append(dict(item=item, out=out, desc=desc, dW=dW, db=db, scratch=scratch,
@@ -254,16 +257,16 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
     if open_reduce:
         part, nchunk = ctypes.c_void_p(), ctypes.c_int32()
         rc = _lib.get().dcll_conv_lif_backward_open(
-            ctypes.byref(desc), ptr(eps1), ptr(v), ptr(pv_pooled), ptr(c(g_p)), ptr(c(g_o) if want_out else None),
-            ptr(c(g_pv)), ptr(c(g_v)), ptr(i2o_W), ptr(d_outW), ptr(d_outb), ptr(scratch), n_scratch, B,
+            ctypes.byref(desc), ptr(eps1), ptr(v), ptr(pv_pooled), ptr(gp_), ptr(go_),
+            ptr(gpv_), ptr(gv_), ptr(i2o_W), ptr(d_outW), ptr(d_outb), ptr(scratch), n_scratch, B,
             ctypes.byref(part), ctypes.byref(nchunk), stream_ptr())
         check(rc, "dcll_conv_lif_backward_open")
         out['parts'] = dict(part=part.value, nchunk=nchunk.value, c_out=desc.c_out,
                             rowlen=(desc.c_in // desc.groups) * desc.kh * desc.kw + 1, dW=dW, db=db, keep=scratch)
         return dW, db, d_outW, d_outb
     rc = _lib.get().dcll_conv_lif_backward(
-        ctypes.byref(desc), ptr(eps1), ptr(v), ptr(pv_pooled), ptr(c(g_p)), ptr(c(g_o) if want_out else None),
-        ptr(c(g_pv)), ptr(c(g_v)), ptr(i2o_W), ptr(dW), ptr(db), ptr(d_outW), ptr(d_outb), ptr(scratch), n_scratch, B,
+        ctypes.byref(desc), ptr(eps1), ptr(v), ptr(pv_pooled), ptr(gp_), ptr(go_),
+        ptr(gpv_), ptr(gv_), ptr(i2o_W), ptr(dW), ptr(db), ptr(d_outW), ptr(d_outb), ptr(scratch), n_scratch, B,
         stream_ptr())
     check(rc, "dcll_conv_lif_backward")
     return dW, db, d_outW, d_outb
@@ -341,16 +344,17 @@ def dense_lif_backward(desc, eps1, pv, g_p, g_pv, g_v, i2o_W, out=None, open_red
     if scratch is None or scratch.numel() != n_scratch:
         scratch = out['bwd_scratch'] = torch.empty((n_scratch,), device=dev, dtype=torch.float32)
     c = lambda t: None if t is None else _f32(t, "grad").contiguous()
+    pv_, gp_, gpv_, gv_ = pv.contiguous(), c(g_p), c(g_pv), c(g_v)      # (locals: see conv_lif_backward)
     if open_reduce:
         part, nchunk = ctypes.c_void_p(), ctypes.c_int32()
         rc = _lib.get().dcll_dense_lif_backward_open(
-            ctypes.byref(desc), ptr(eps1), ptr(pv.contiguous()), ptr(c(g_p)), ptr(c(g_pv)), ptr(c(g_v)), ptr(i2o_W), ptr(scratch),
+            ctypes.byref(desc), ptr(eps1), ptr(pv_), ptr(gp_), ptr(gpv_), ptr(gv_), ptr(i2o_W), ptr(scratch),
             n_scratch, B, ctypes.byref(part), ctypes.byref(nchunk), stream_ptr())
         check(rc, "dcll_dense_lif_backward_open")
         out['parts'] = dict(part=part.value, nchunk=nchunk.value, c_out=nout, rowlen=nin + 1, dW=dW, db=db, keep=scratch)
         return dW, db
     rc = _lib.get().dcll_dense_lif_backward(
-        ctypes.byref(desc), ptr(eps1), ptr(pv.contiguous()), ptr(c(g_p)), ptr(c(g_pv)), ptr(c(g_v)), ptr(i2o_W), ptr(dW), ptr(db),
+        ctypes.byref(desc), ptr(eps1), ptr(pv_), ptr(gp_), ptr(gpv_), ptr(gv_), ptr(i2o_W), ptr(dW), ptr(db),
         ptr(scratch), n_scratch, B, stream_ptr())
     check(rc, "dcll_dense_lif_backward")
     return dW, db
