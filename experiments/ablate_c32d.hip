@@ -1,16 +1,20 @@
-// Stage-phase timing of k_lif_seq_c32d (diagnostic, not product).
+// Stage-phase timing of k_lif_seq_c32rp and k_lif_seq_c32d (diagnostic, not product).
 //   ./ablate_c32d            the kernel alone
 //   ./ablate_c32d co         with the co-resident readout (k_readout_direct, <= 64 VGPRs, no LDS) running on a second,
 //                            lower-priority stream over the previous pv buffer — what test_sequence(overlap_readout=True)
 //                            does: how much does a stage of the layer kernel stretch?
 //   ./ablate_c32d presig     pv_presigmoid (round 3): the epilogue stores v instead of sigmoid(v) — launch time and the
 //                            stamps of the non-MFMA phase with and without the four sigmoids per wave and stage
+//   ./ablate_c32d tp         the time-paired k_lif_seq_c32d (a tile = one image row at two timesteps, every padded tap row
+//                            skipped) against the row-paired k_lif_seq_c32rp: launch times and stage stamps of both, and
+//                            the time-paired chain phase alone (no trace update, no epilogue)
 #include "../snn_modulation_classification_amd/csrc/dcll_hip.hip"
 #include <vector>
 int main(int argc, char **argv)
 {
     const bool presig = argc > 1 && argv[1][0] == 'p';
-    const bool co = argc > 1 && !presig;
+    const bool tp = argc > 1 && argv[1][0] == 't';
+    const bool co = argc > 1 && !presig && !tp;
     const int B = 1024, T = 128;
     size_t nin = (size_t)T * B * 32 * 8;
     uint32_t *spk_in, *spk_out; float *W, *bias, *tau4, *e0, *e1, *arp, *pv; unsigned long long *dbg;
@@ -42,25 +46,57 @@ int main(int argc, char **argv)
     auto launch_side = [&](int n) {
         for (int i = 0; i < n; ++i) dcll_launch_readout_direct(pv2, Wro, nullptr, ro, (long)T * B, 8192, 24, side);
     };
+    if (tp) {
+        const char *names[3] = {"k_lif_seq_c32rp (row-paired)", "k_lif_seq_c32d (time-paired)", "k_lif_seq_c32d, chain phase only"};
+        for (int mode = 0; mode < 3; ++mode) {
+            for (int rep = 0; rep < 3 && mode < 2; ++rep) {
+                hipMemset(e0, 0, ns * 4); hipMemset(e1, 0, ns * 4); hipMemset(arp, 0, ns * 4);
+                hipEventRecord(a);
+                if (mode == 0)
+                    hipLaunchKernelGGL((k_lif_seq_c32rp<true, 1, 0>), dim3(B), dim3(512), 0, 0, spk_in, dcll_wsrc{W, nullptr, nullptr}, bias, tau4, e0, e1, arp, spk_out, pv, (float *)nullptr, T, B, 0.65f, 1.0f);
+                else
+                    hipLaunchKernelGGL((k_lif_seq_c32d<true, 1, 0>), dim3(B), dim3(512), 0, 0, spk_in, dcll_wsrc{W, nullptr, nullptr}, bias, tau4, e0, e1, arp, spk_out, pv, (float *)nullptr, T, B, 0.65f, 1.0f);
+                hipEventRecord(b); hipEventSynchronize(b);
+                float ms; hipEventElapsedTime(&ms, a, b);
+                printf("%s B=%d T=%d: %.3f ms\n", names[mode], B, T, ms);
+            }
+            hipMemset(dbg, 0, 4096);
+            if (mode == 0)
+                hipLaunchKernelGGL((k_lif_seq_c32rp<true, 1, 1>), dim3(B), dim3(512), 0, 0, spk_in, dcll_wsrc{W, nullptr, nullptr}, bias, tau4, e0, e1, arp, spk_out, pv, (float *)dbg, T, B, 0.65f, 1.0f);
+            else if (mode == 1)
+                hipLaunchKernelGGL((k_lif_seq_c32d<true, 1, 1>), dim3(B), dim3(512), 0, 0, spk_in, dcll_wsrc{W, nullptr, nullptr}, bias, tau4, e0, e1, arp, spk_out, pv, (float *)dbg, T, B, 0.65f, 1.0f);
+            else
+                hipLaunchKernelGGL((k_lif_seq_c32d<true, 1, 9>), dim3(B), dim3(512), 0, 0, spk_in, dcll_wsrc{W, nullptr, nullptr}, bias, tau4, e0, e1, arp, spk_out, pv, (float *)dbg, T, B, 0.65f, 1.0f);
+            hipDeviceSynchronize();
+            unsigned long long h4[64];
+            hipMemcpy(h4, dbg, 512, hipMemcpyDeviceToHost);
+            const double nst4 = 4.0 * T + 8;
+            printf("%s: cycles per stage | non-MFMA phase | barrier 2 | chains + slot write | barrier 1\n", names[mode]);
+            for (int w = 0; w < 8; ++w)
+                printf("  w%d: %8.0f | %7.0f | %7.0f | %7.0f | %7.0f\n", w, h4[w * 8] / nst4, h4[w * 8 + 1] / nst4, h4[w * 8 + 2] / nst4,
+                       h4[w * 8 + 3] / nst4, h4[w * 8 + 4] / nst4);
+        }
+        return 0;
+    }
     if (presig) {
         for (int mode = 0; mode < 2; ++mode) {
             float best = 1e30f;
             for (int rep = 0; rep < 4; ++rep) {
                 hipEventRecord(a);
                 if (mode == 0)
-                    hipLaunchKernelGGL((k_lif_seq_c32d<true, 1, 0>), dim3(B), dim3(512), 0, 0, spk_in, dcll_wsrc{W, nullptr, nullptr}, bias, tau4, e0, e1, arp, spk_out, pv, (float *)nullptr, T, B, 0.65f, 1.0f);
+                    hipLaunchKernelGGL((k_lif_seq_c32rp<true, 1, 0>), dim3(B), dim3(512), 0, 0, spk_in, dcll_wsrc{W, nullptr, nullptr}, bias, tau4, e0, e1, arp, spk_out, pv, (float *)nullptr, T, B, 0.65f, 1.0f);
                 else
-                    hipLaunchKernelGGL((k_lif_seq_c32d<true, 2, 0>), dim3(B), dim3(512), 0, 0, spk_in, dcll_wsrc{W, nullptr, nullptr}, bias, tau4, e0, e1, arp, spk_out, (float *)nullptr, pv, T, B, 0.65f, 1.0f);
+                    hipLaunchKernelGGL((k_lif_seq_c32rp<true, 2, 0>), dim3(B), dim3(512), 0, 0, spk_in, dcll_wsrc{W, nullptr, nullptr}, bias, tau4, e0, e1, arp, spk_out, (float *)nullptr, pv, T, B, 0.65f, 1.0f);
                 hipEventRecord(b); hipEventSynchronize(b);
                 float ms; hipEventElapsedTime(&ms, a, b);
                 if (ms < best) best = ms;
             }
-            printf("k_lif_seq_c32d B=%d T=%d, buffer = %s: %.3f ms (best of 4)\n", B, T, mode ? "v (pv_presigmoid)" : "sigmoid(v)", best);
+            printf("k_lif_seq_c32rp B=%d T=%d, buffer = %s: %.3f ms (best of 4)\n", B, T, mode ? "v (pv_presigmoid)" : "sigmoid(v)", best);
             // stamps: the debug area is the head of the v output (OUT = 3 / 2: both variants also write v there first)
             if (mode == 0)
-                hipLaunchKernelGGL((k_lif_seq_c32d<true, 3, 1>), dim3(B), dim3(512), 0, 0, spk_in, dcll_wsrc{W, nullptr, nullptr}, bias, tau4, e0, e1, arp, spk_out, pv, (float *)dbg_v, T, B, 0.65f, 1.0f);
+                hipLaunchKernelGGL((k_lif_seq_c32rp<true, 3, 1>), dim3(B), dim3(512), 0, 0, spk_in, dcll_wsrc{W, nullptr, nullptr}, bias, tau4, e0, e1, arp, spk_out, pv, (float *)dbg_v, T, B, 0.65f, 1.0f);
             else
-                hipLaunchKernelGGL((k_lif_seq_c32d<true, 2, 1>), dim3(B), dim3(512), 0, 0, spk_in, dcll_wsrc{W, nullptr, nullptr}, bias, tau4, e0, e1, arp, spk_out, (float *)nullptr, (float *)dbg_v, T, B, 0.65f, 1.0f);
+                hipLaunchKernelGGL((k_lif_seq_c32rp<true, 2, 1>), dim3(B), dim3(512), 0, 0, spk_in, dcll_wsrc{W, nullptr, nullptr}, bias, tau4, e0, e1, arp, spk_out, (float *)nullptr, (float *)dbg_v, T, B, 0.65f, 1.0f);
             hipDeviceSynchronize();
             unsigned long long h3[64];
             hipMemcpy(h3, dbg_v, 512, hipMemcpyDeviceToHost);
@@ -74,22 +110,22 @@ int main(int argc, char **argv)
     }
     for (int rep = 0; rep < 3 && !co; ++rep) {
         hipEventRecord(a);
-        hipLaunchKernelGGL((k_lif_seq_c32d<true, 1, 0>), dim3(B), dim3(512), 0, 0, spk_in, dcll_wsrc{W, nullptr, nullptr}, bias, tau4, e0, e1, arp, spk_out, pv, (float *)nullptr, T, B, 0.65f, 1.0f);
+        hipLaunchKernelGGL((k_lif_seq_c32rp<true, 1, 0>), dim3(B), dim3(512), 0, 0, spk_in, dcll_wsrc{W, nullptr, nullptr}, bias, tau4, e0, e1, arp, spk_out, pv, (float *)nullptr, T, B, 0.65f, 1.0f);
         hipEventRecord(b); hipEventSynchronize(b);
         float ms; hipEventElapsedTime(&ms, a, b);
-        printf("k_lif_seq_c32d B=%d T=%d: %.2f ms (ideal at 157.3 TF: %.2f)\n", B, T, ms, 2.0 * 32 * 1568 * 256 * (double)T * B / 157.3e12 * 1e3);
+        printf("k_lif_seq_c32rp B=%d T=%d: %.2f ms (ideal at 157.3 TF: %.2f)\n", B, T, ms, 2.0 * 32 * 1568 * 256 * (double)T * B / 157.3e12 * 1e3);
     }
     if (!co) {
         // what do the LDS bank conflicts of the B-fragment reads cost?  Same kernel with the tile's second image row read
         // 16 instead of 19 floats behind the first (conflict free, WRONG data — timing only), same stamps.
         for (int rep = 0; rep < 3; ++rep) {
             hipEventRecord(a);
-            hipLaunchKernelGGL((k_lif_seq_c32d<true, 1, 2>), dim3(B), dim3(512), 0, 0, spk_in, dcll_wsrc{W, nullptr, nullptr}, bias, tau4, e0, e1, arp, spk_out, pv, (float *)nullptr, T, B, 0.65f, 1.0f);
+            hipLaunchKernelGGL((k_lif_seq_c32rp<true, 1, 2>), dim3(B), dim3(512), 0, 0, spk_in, dcll_wsrc{W, nullptr, nullptr}, bias, tau4, e0, e1, arp, spk_out, pv, (float *)nullptr, T, B, 0.65f, 1.0f);
             hipEventRecord(b); hipEventSynchronize(b);
             float ms; hipEventElapsedTime(&ms, a, b);
-            printf("k_lif_seq_c32d, conflict-free B reads (wrong data): %.2f ms\n", ms);
+            printf("k_lif_seq_c32rp, conflict-free B reads (wrong data): %.2f ms\n", ms);
         }
-        hipLaunchKernelGGL((k_lif_seq_c32d<true, 1, 3>), dim3(B), dim3(512), 0, 0, spk_in, dcll_wsrc{W, nullptr, nullptr}, bias, tau4, e0, e1, arp, spk_out, pv, (float *)dbg, T, B, 0.65f, 1.0f);
+        hipLaunchKernelGGL((k_lif_seq_c32rp<true, 1, 3>), dim3(B), dim3(512), 0, 0, spk_in, dcll_wsrc{W, nullptr, nullptr}, bias, tau4, e0, e1, arp, spk_out, pv, (float *)dbg, T, B, 0.65f, 1.0f);
         unsigned long long h2[64];
         hipMemcpy(h2, dbg, 512, hipMemcpyDeviceToHost);
         const double nst2 = 4.0 * T + 8;
@@ -104,11 +140,11 @@ int main(int argc, char **argv)
         launch_side(40);                            // far longer than the layer kernel
         hipEventRecord(a, hot);
     }
-    hipLaunchKernelGGL((k_lif_seq_c32d<true, 1, 1>), dim3(B), dim3(512), 0, hot, spk_in, dcll_wsrc{W, nullptr, nullptr}, bias, tau4, e0, e1, arp, spk_out, pv, (float *)dbg, T, B, 0.65f, 1.0f);
+    hipLaunchKernelGGL((k_lif_seq_c32rp<true, 1, 1>), dim3(B), dim3(512), 0, hot, spk_in, dcll_wsrc{W, nullptr, nullptr}, bias, tau4, e0, e1, arp, spk_out, pv, (float *)dbg, T, B, 0.65f, 1.0f);
     if (co) {
         hipEventRecord(b, hot); hipEventSynchronize(b);
         float ms; hipEventElapsedTime(&ms, a, b);
-        printf("k_lif_seq_c32d B=%d T=%d with the co-resident readout running: %.2f ms\n", B, T, ms);
+        printf("k_lif_seq_c32rp B=%d T=%d with the co-resident readout running: %.2f ms\n", B, T, ms);
     }
     hipDeviceSynchronize();
     unsigned long long h[64];

@@ -12,7 +12,8 @@
 // -ffp-contract=off is part of the arithmetic contract: the trace lines are three separately rounded ops.
 //
 // Kernels
-//   k_lif_seq_c32d     the hot kernel (T >= 8): k_lif_seq_c32 with two pixel tiles per wave and stage — see its header.
+//   k_lif_seq_c32d     the hot kernel (even T >= 8): k_lif_seq_c32 with two tiles per wave and stage, a tile = one image row at
+//                      two timesteps — see its header.   k_lif_seq_c32rp: its row-paired predecessor, kept for odd T >= 8.
 //   k_lif_seq_c32      one 32->32 7x7 layer, ALL T timesteps, one sample per workgroup (short sequences, per-step calls).
 //                      8 waves; wave w owns input channels 4w..4w+3 (a K-slice of the implicit GEMM):
 //                      their eps0/eps1 traces (registers + a zero-padded LDS image) and the 2x49 weight
@@ -1689,7 +1690,7 @@ __global__ __launch_bounds__(512) void k_lif_seq_c32(const uint32_t *__restrict_
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// k_lif_seq_c32d — k_lif_seq_c32 with TWO pixel tiles per wave and stage (the long-sequence variant).
+// k_lif_seq_c32rp — k_lif_seq_c32 with TWO pixel tiles per wave and stage (the long-sequence variant).
 //
 // Same data layout, same weight-stationary systolic chain, same pinned order.  Per stage a wave runs the K-slices of
 // the tile pair (2p, 2p+1) — image rows 4p..4p+3 — as two INDEPENDENT accumulator chains:
@@ -1712,7 +1713,7 @@ __global__ __launch_bounds__(512) void k_lif_seq_c32(const uint32_t *__restrict_
 // ------------------------------------------------------------------------------------------------------------
 // DBG is a diagnostic knob for experiments/ablate_c32d.hip only (s_memtime stamps of workgroup 0 into v_out).
 template <bool REFRACTORY, int OUT, int DBG = 0>     // OUT bit0: pv, bit1: v
-__global__ __launch_bounds__(512) void k_lif_seq_c32d(const uint32_t *__restrict__ spk_in, const dcll_wsrc W,
+__global__ __launch_bounds__(512) void k_lif_seq_c32rp(const uint32_t *__restrict__ spk_in, const dcll_wsrc W,
                                                        const float *__restrict__ bias, const float *__restrict__ tau4,
                                                        float *__restrict__ eps0_g, float *__restrict__ eps1_g,
                                                        float *__restrict__ arp_g, uint32_t *__restrict__ spk_out,
@@ -1998,6 +1999,378 @@ __global__ __launch_bounds__(512) void k_lif_seq_c32d(const uint32_t *__restrict
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr)
                 arp_g[(b * 32 + rr + 8 * wq + 4 * h) * 256 + 32 * (2 * k + wpar) + j] = arp[k][rr];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// k_lif_seq_c32d — THE HOT KERNEL (16x16, even T >= 8): the tile of the MFMA is ONE image row at TWO timesteps.
+//
+// The 32 -> 32 convolution of step t reads only this layer's input traces eps1(t), which depend on the input spikes (in
+// HBM for all T) and not on this layer's output; the only recurrence through the output is the refractory trace, which is
+// elementwise and lives in the epilogue.  So the 32 "pixels" of v_mfma_f32_32x32x2_f32 are: lanes 0..15 image row r at step
+// t, lanes 16..31 the same row at step t + 1, read from two LDS images ("t" and "t+1", TP_IMGP floats apart).  Both halves
+// of the tile have the same tap-row validity, so EVERY tap row that lies in the zero padding is skipped exactly
+// (fmaf(w, +0, acc) == acc): 100 of the 112 (image row, tap row) combinations remain, where the row-paired tiles of
+// k_lif_seq_c32rp keep 104.  Weight fragments, accumulator layout, slot layout and the pinned chain bias -> (cp, ky, kx, h)
+// are those of k_lif_seq_c32.
+//
+// A step pair takes 8 stages; in its stage s a wave runs the chains of the image rows TP_ROW_A[s] and TP_ROW_B[s].  The four
+// border pairs have 11 live tap rows (154 MFMAs per wave), the four inner ones 14 (196); the order reads 11 11 14 14 11 11 14 14
+// and the two waves of a SIMD are two chain positions apart, so every SIMD carries 350 MFMAs in every stage (364 before).
+// Source row rho is tap row ky = rho - r + 3 of output row r; both chains walk rho upward and share the B fragments.
+//
+// The two images are updated IN PLACE: wave w is the only reader and the only writer of channels 4w..4w+3.  At the start of
+// its stage s it advances the image rows 2m, 2m+1 (m = (s + 3) & 7) by two steps — eps1(t+2) from the "t+1" image into the
+// "t" image, eps1(t+3) from that value into the "t+1" image, eps0 in registers: in the stages 0..4 to the step pair the
+// wave is in (no earlier stage of the pair reads these rows), in the stages 5..7 to the next one (no later stage reads
+// them).  tp_schedule_ok() checks that, and the balance above, at compile time.
+//
+// Everything a stage indexes registers with is a compile-time function of s = (g - w) & 7 (one switch per stage): the eps0
+// group s, the chain shapes, and the refractory traces of the epilogue share of stage g, which is tile pair (s + w) & 7 —
+// its image row is a scalar.  Epilogue share of wave (wq = w & 3, wpar = w >> 2): quad wq of tile wpar; lane L takes
+// pixel L & 15 and the two channels 8 wq + 4 (L >> 5) + 2 ((L >> 4) & 1) + {0, 1} at BOTH steps (the refractory update of
+// t + 1 needs that of t).  pv / v leave as 64-byte row pieces, the spikes as 16-bit halves of the packed words.
+// DBG (experiments/ablate_c32d.hip only): bit 0 s_memtime stamps of workgroup 0 into v_out, bit 3 chain phase only (no
+// trace update, no epilogue: WRONG results, timing).
+// ------------------------------------------------------------------------------------------------------------
+constexpr int TP_IMGP = IMG_FLOATS + 20;    // pitch of the two images: 16 mod 32, the two halves of a B fragment on disjoint banks
+static_assert(TP_IMGP % 32 == 16 && TP_IMGP >= IMG_FLOATS, "image pitch");
+constexpr int TP_ROW_A[8] = {0, 1, 4, 6, 12, 13, 8, 10}, TP_ROW_B[8] = {3, 2, 5, 7, 15, 14, 9, 11};
+constexpr int tp_lo(int r) { return r - 3 < 0 ? 0 : r - 3; }            // first / last source row of output row r
+constexpr int tp_hi(int r) { return r + 3 > 15 ? 15 : r + 3; }
+constexpr int tp_trace_m(int s) { return (s + 3) & 7; }                  // image rows 2m, 2m+1 advanced at the start of stage s
+constexpr bool tp_trace_next(int s) { return s >= 5; }                   // ... to the next step pair (else: to the current one)
+constexpr bool tp_reads(int s, int rho) { return rho >= tp_lo(TP_ROW_A[s]) && rho <= tp_hi(TP_ROW_B[s]); }
+constexpr uint32_t tp_pack(const int (&r)[8])
+{
+    uint32_t p = 0;
+    for (int i = 0; i < 8; ++i) p |= (uint32_t)r[i] << (4 * i);
+    return p;
+}
+constexpr bool tp_schedule_ok()
+{
+    int seen = 0, mseen = 0;
+    for (int s = 0; s < 8; ++s) {
+        if (TP_ROW_A[s] >= TP_ROW_B[s]) return false;                   // the union of the source rows is lo(A) .. hi(B)
+        if (tp_lo(TP_ROW_A[s]) > tp_lo(TP_ROW_B[s]) || tp_hi(TP_ROW_A[s]) > tp_hi(TP_ROW_B[s])) return false;
+        if (tp_lo(TP_ROW_B[s]) > tp_hi(TP_ROW_A[s]) + 1) return false;  // ... without a gap
+        seen |= (1 << TP_ROW_A[s]) | (1 << TP_ROW_B[s]);
+        // balance: the partner wave of the SIMD is two chain positions away
+        const int s2 = (s + 2) & 7;
+        const int n = tp_hi(TP_ROW_A[s]) - tp_lo(TP_ROW_A[s]) + tp_hi(TP_ROW_B[s]) - tp_lo(TP_ROW_B[s]) + 2;
+        const int n2 = tp_hi(TP_ROW_A[s2]) - tp_lo(TP_ROW_A[s2]) + tp_hi(TP_ROW_B[s2]) - tp_lo(TP_ROW_B[s2]) + 2;
+        if (n + n2 != 25) return false;
+        // rolling update of rows 2m, 2m+1 at the start of stage s
+        const int m = tp_trace_m(s);
+        mseen |= 1 << m;
+        for (int rho = 2 * m; rho < 2 * m + 2; ++rho) {
+            if (tp_trace_next(s)) {
+                for (int u = s; u < 8; ++u) if (tp_reads(u, rho)) return false;     // still needed at the old steps
+            } else {
+                for (int u = 0; u < s; ++u) if (tp_reads(u, rho)) return false;     // was needed at the new steps
+                if (rho == tp_lo(TP_ROW_A[s])) return false;    // the stage's first B row is fetched before the update
+            }
+        }
+    }
+    return seen == 0xffff && mseen == 0xff;
+}
+static_assert(tp_schedule_ok(), "k_lif_seq_c32d: tile order / rolling trace schedule");
+
+template <bool REFRACTORY, int OUT, int DBG = 0>     // OUT bit0: pv, bit1: v
+__global__ __launch_bounds__(512) void k_lif_seq_c32d(const uint32_t *__restrict__ spk_in, const dcll_wsrc W,
+                                                       const float *__restrict__ bias, const float *__restrict__ tau4,
+                                                       float *__restrict__ eps0_g, float *__restrict__ eps1_g,
+                                                       float *__restrict__ arp_g, uint32_t *__restrict__ spk_out,
+                                                       float *__restrict__ pv_out, float *__restrict__ v_out, int T,
+                                                       int B, float alpharp, float wrp)
+{
+    __shared__ __attribute__((aligned(16))) float lds[2 * TP_IMGP + (NWAVE * 2 + 1) * SLOT_FLOATS];
+    float *slots = lds + 2 * TP_IMGP;           // [wave][tile A / B of the pair][16 x 64]
+    float *sbias = slots + NWAVE * 2 * SLOT_FLOATS;     // the bias as a slot-shaped tile: wave 0's chain input
+    const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, j = lane & 31, px = lane & 15, rb = (lane >> 4) & 1;
+    // chain position w of hardware wave i: 0 1 4 5 2 3 6 7 — the two waves of a SIMD (i, i + 4) are TWO positions apart
+    const int wi = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int w = (wi & 1) | ((wi & 4) >> 1) | ((wi & 2) << 1);
+    const int wq = w & 3, wpar = w >> 2;        // my epilogue share: quad wq of the pair's tile wpar
+    const long b = blockIdx.x;
+    const int NP = T >> 1;                      // step pairs
+    __builtin_amdgcn_s_setprio(3);              // (see k_lif_seq_c32rp)
+
+    for (int i = tid; i < 2 * TP_IMGP; i += 512) lds[i] = 0.0f;
+    // slot layout: float4 c of lane l = accumulator registers 4c..4c+3 = channels (r&3) + 8c + 4(l>>5)
+    for (int i = tid; i < SLOT_FLOATS; i += 512) sbias[i] = bias[(i & 3) + 8 * (i >> 8) + 4 * ((i >> 7) & 1)];
+
+    float wf[2][49];
+    load_wf_c32(W, j, w, h, wf);
+
+    // traces: register group s, element e = channel 4w + 2e + h, image row 2 tp_trace_m(s) + rb, pixel px; eps1 in both
+    // images at float offset toff + e*2*CHF + 2m*ROWF
+    float e0[8][2];
+    const int toff = (4 * w + h) * CHF + (rb + 3) * ROWF + px + 3;
+    float ta[2], tm[2], tas[2], ts[2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        ta[e] = tau4[0 * 32 + 4 * w + 2 * e + h]; tm[e] = tau4[1 * 32 + 4 * w + 2 * e + h];
+        tas[e] = tau4[2 * 32 + 4 * w + 2 * e + h]; ts[e] = tau4[3 * 32 + 4 * w + 2 * e + h];
+    }
+    // input spikes: word m of a channel = image rows 2m, 2m+1; the words of channels 2e, 2e+1 side by side ARE the lane mask
+    const uint32_t *in_wave = spk_in + (b * 32 + 4 * w) * 8;
+    const long in_step = (long)B * 32 * 8;
+    auto in_mask = [&](long t, int e, int m) -> unsigned long long {
+        const uint32_t *ip = in_wave + t * in_step + 2 * e * 8 + m;
+        return (unsigned long long)ip[0] | ((unsigned long long)ip[8] << 32);
+    };
+    __syncthreads();        // images zeroed
+
+    // prologue: state from HBM, advanced to steps 0 and 1 -> the two images
+    static_for<0, 8>([&](auto SC) {
+        constexpr int S = decltype(SC)::value, M = tp_trace_m(S);
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const long gidx = (b * 32 + 4 * w + 2 * e + h) * 256 + 32 * M + j;
+            e0[S][e] = eps0_g[gidx];
+            float e1 = eps1_g[gidx];
+            float *dst = lds + toff + e * 2 * CHF + 2 * M * ROWF;
+            trace_update((float)((in_mask(0, e, M) >> lane) & 1ull), ta[e], tm[e], tas[e], ts[e], e0[S][e], e1);
+            dst[0] = e1;
+            trace_update((float)((in_mask(1, e, M) >> lane) & 1ull), ta[e], tm[e], tas[e], ts[e], e0[S][e], e1);
+            dst[TP_IMGP] = e1;
+        }
+    });
+    // refractory trace of my epilogue shares: group s = tile pair (s + w) & 7, its tile wpar, channels ech + {0, 1}
+    const uint32_t rowpk = wpar ? tp_pack(TP_ROW_B) : tp_pack(TP_ROW_A);
+    const int ech = 8 * wq + 4 * h + 2 * rb;
+    float arp[8][2];
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+        const int re = (rowpk >> (4 * ((s + w) & 7))) & 15;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) arp[s][k] = REFRACTORY ? arp_g[(b * 32 + ech + k) * 256 + re * 16 + px] : 0.0f;
+    }
+
+    // per-lane base of the B-fragment reads: channel 4w + h, image j >> 4, column j & 15
+    const int bbase = (4 * w + h) * CHF + (j >> 4) * TP_IMGP + (j & 15);
+    // epilogue: my two values of a step in the slot of wave 7, and the lane byte offsets of the stores
+    const int eslot = (7 * 2 + wpar) * SLOT_FLOATS + (wq * 64 + h * 32 + px) * 4 + 2 * rb;
+    const unsigned eoff = 4u * ((4 * h + 2 * rb) * 256 + px);
+    // spike halves: lane px < 4 of every 16 stores the half word of (channel ech + (px & 1), step px >> 1)
+    const unsigned soff = (unsigned)(px >> 1) * ((unsigned)B * 1024u) + 32u * (4 * h + 2 * rb + (px & 1));
+#pragma unroll
+    for (int s = 0; s < 8; ++s)
+#pragma unroll
+        for (int k = 0; k < 2; ++k) asm volatile("" ::"v"(arp[s][k]), "v"(e0[s][k]));
+#pragma unroll
+    for (int cp = 0; cp < 2; ++cp)
+#pragma unroll
+        for (int k = 0; k < 49; ++k) asm volatile("" ::"v"(wf[cp][k]));
+    __syncthreads();
+
+    unsigned long long dbg[4] = {0, 0, 0, 0}, dbg_t0 = 0;       // DBG only: non-MFMA phase, barrier 2, chains, barrier 1
+    if (DBG & 1) dbg_t0 = __builtin_amdgcn_s_memtime();
+    // inputs of the trace share of a wave's next stage (eps1 of the "t+1" image, input masks), fetched one stage ahead
+    float sv[2] = {0.f, 0.f};
+    unsigned long long wm[2][2] = {{0, 0}, {0, 0}};
+    // does the wave advance rows in stage s of its step pair P?  (the prologue did pair 0)
+    auto tracing = [&](const int q, const int s) {
+        const int P = q >> 3;
+        return !(DBG & 8) && q >= 0 && (tp_trace_next(s) ? P + 1 < NP : (P >= 1 && P < NP));
+    };
+    auto fetch_trace_inputs = [&](const int q, auto SC) {
+        constexpr int S = decltype(SC)::value, M = tp_trace_m(S);
+        if (tracing(q, S)) {
+            const long t2 = 2 * ((q >> 3) + (tp_trace_next(S) ? 1 : 0));
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                sv[e] = lds[TP_IMGP + toff + e * 2 * CHF + 2 * M * ROWF];
+                wm[e][0] = in_mask(t2, e, M);
+                wm[e][1] = in_mask(t2 + 1, e, M);
+            }
+        }
+    };
+    // one stage; S = (g - w) & 7 at compile time
+    auto stage = [&](const int g, auto SC) {
+        constexpr int S = decltype(SC)::value, RA = TP_ROW_A[S], RB = TP_ROW_B[S];
+        constexpr int LO = tp_lo(RA), HI = tp_hi(RB), NRH = HI - LO + 1, NR = 2 * NRH;
+        unsigned long long st0 = 0, st1 = 0, st2 = 0, st3 = 0;
+        if (DBG & 1) st0 = __builtin_amdgcn_s_memtime();
+        const int q = g - w;
+        const bool active = q >= 0 && q < 8 * NP;
+        // ---- (0) everything this stage reads from LDS goes out first: chain inputs out of the slots ----
+        f32x16 accA, accB;
+        if (active) {
+            const float *inA = (w == 0) ? sbias : slots + ((w - 1) * 2) * SLOT_FLOATS;
+            const float *inB = (w == 0) ? sbias : slots + ((w - 1) * 2 + 1) * SLOT_FLOATS;
+            const f32x4 *spa = (const f32x4 *)inA + lane, *spb = (const f32x4 *)inB + lane;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                f32x4 va = spa[c * 64], vb = spb[c * 64];
+                accA[4 * c + 0] = va[0]; accA[4 * c + 1] = va[1]; accA[4 * c + 2] = va[2]; accA[4 * c + 3] = va[3];
+                accB[4 * c + 0] = vb[0]; accB[4 * c + 1] = vb[1]; accB[4 * c + 2] = vb[2]; accB[4 * c + 3] = vb[3];
+            }
+        }
+        //   epilogue share: my channels of tile wpar of the pair qe = g - 8 that wave 7 finished last stage, both steps
+        const int qe = g - 8;
+        const bool epi = !(DBG & 8) && qe >= 0 && qe < 8 * NP;
+        f32x2 v0 = {0.f, 0.f}, v1 = {0.f, 0.f};
+        if (epi) {
+            v0 = *(const f32x2 *)(slots + eslot);
+            v1 = *(const f32x2 *)(slots + eslot + 64);
+        }
+        //   first B-fragment row of the chains: bases of my two channel pairs as opaque LDS addresses, every read of the
+        //   chains is base + immediate (see k_lif_seq_c32rp)
+        lds_cfloat *ib0 = (lds_cfloat *)(lds + bbase + (LO + 3) * ROWF), *ib1 = (lds_cfloat *)(lds + bbase + (LO + 3) * ROWF + 2 * CHF);
+        asm volatile("" : "+v"(ib0), "+v"(ib1));
+        float bq[2][7];
+        if (active) {
+#pragma unroll
+            for (int kx = 0; kx < 7; ++kx) bq[0][kx] = ib0[kx];
+        }
+        // ---- (2) trace share: rows 2M, 2M+1 of my channels, two steps in place (every op rounded separately) ----
+        if (tracing(q, S)) {
+            float *dst = lds + toff + 2 * tp_trace_m(S) * ROWF;
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                float e1 = sv[e];
+#pragma unroll
+                for (int dt = 0; dt < 2; ++dt) {
+                    float a;                                    // x * tau_s with x in {0,1}: exact select
+                    asm("v_cndmask_b32 %0, 0, %1, %2" : "=v"(a) : "v"(ts[e]), "s"(wm[e][dt]));
+                    const float bb = tas[e] * e0[S][e];
+                    e0[S][e] = a + bb;
+                    const float cc = ta[e] * e1;
+                    const float dd = e0[S][e] * tm[e];
+                    e1 = cc + dd;
+                    dst[e * 2 * CHF + dt * TP_IMGP] = e1;
+                }
+            }
+        }
+        // ---- (1) epilogue share ----
+        if (epi) {
+            const int te = 2 * (qe >> 3);
+            const int re = (rowpk >> (4 * (g & 7))) & 15;       // image row of my tile
+            const long ubase = (((long)te * B + b) * 32 + 8 * wq) * 256, ustep = (long)B * 32 * 256;
+            float vv[2][2];
+            unsigned long long mk[2][2];
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                bool s0, s1;
+                if (REFRACTORY) {
+                    vv[k][0] = refractory(v0[k], arp[S][k], alpharp, wrp, s0);
+                    vv[k][1] = refractory(v1[k], arp[S][k], alpharp, wrp, s1);
+                } else {
+                    vv[k][0] = v0[k]; vv[k][1] = v1[k];
+                    s0 = v0[k] > 0.0f; s1 = v1[k] > 0.0f;
+                }
+                mk[k][0] = __ballot(s0); mk[k][1] = __ballot(s1);
+            }
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt) {
+                const auto prs = tile_rsrc(pv_out + ubase + dt * ustep), vrs = tile_rsrc(v_out + ubase + dt * ustep);
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    if (OUT & 1) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(sigmoidf_dev(vv[k][dt])), prs, eoff + 4u * (k * 256), re * 64, 0);
+                    if (OUT & 2) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(vv[k][dt]), vrs, eoff + 4u * (k * 256), re * 64, 0);
+                }
+            }
+            if (spk_out) {
+                uint32_t myword = 0;
+#pragma unroll
+                for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+                    for (int k = 0; k < 2; ++k) {
+                        const uint32_t mine = h ? (uint32_t)(mk[k][dt] >> 32) : (uint32_t)mk[k][dt];
+                        myword = (px == k + 2 * dt) ? mine : myword;
+                    }
+                myword >>= 16 * rb;
+                if (px < 4)
+                    __builtin_amdgcn_raw_buffer_store_b16((unsigned short)myword, tile_rsrc(spk_out + (ubase >> 5)), soff, 4 * (re >> 1) + 2 * (re & 1), 0);
+            }
+        }
+        if (DBG & 1) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); st1 = __builtin_amdgcn_s_memtime(); }
+        // every slot read of this stage has completed before any wave writes its slots again
+        lds_barrier();
+        if (DBG & 1) st2 = __builtin_amdgcn_s_memtime();
+        // inputs of the NEXT stage's trace share: they land while the chains run (nobody else touches my channels, and my
+        // own update of those rows comes a stage later)
+        fetch_trace_inputs(q + 1, std::integral_constant<int, (S + 1) & 7>{});
+        // ---- (3) my K-slice of both chains: source rows LO..HI per channel pair, row rho is tap row rho - RA + 3 of tile A
+        //      and rho - RB + 3 of tile B where those are taps at all; the next row is fetched before the MFMAs of this one ----
+        if (active) {
+#pragma unroll
+            for (int r = 0; r < NR; ++r) {
+                const int cp = r / NRH, rho = LO + r % NRH;
+                if (r + 1 < NR) {
+                    const int cpn = (r + 1) / NRH, rhon = (r + 1) % NRH;
+#pragma unroll
+                    for (int kx = 0; kx < 7; ++kx) bq[(r + 1) & 1][kx] = (cpn ? ib1 : ib0)[rhon * ROWF + kx];
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int kx = 0; kx < 7; ++kx) {
+                    if (rho >= tp_lo(RA) && rho <= tp_hi(RA))
+                        accA = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[cp][(rho - RA + 3) * 7 + kx], bq[r & 1][kx], accA, 0, 0, 0);
+                    if (rho >= tp_lo(RB) && rho <= tp_hi(RB))
+                        accB = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[cp][(rho - RB + 3) * 7 + kx], bq[r & 1][kx], accB, 0, 0, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                if (cp == 1 && rho == tp_hi(RA)) {      // tile A is complete, usually while B still runs
+                    f32x4 *dpa = (f32x4 *)(slots + (w * 2) * SLOT_FLOATS) + lane;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c)
+                        dpa[c * 64] = f32x4{accA[4 * c + 0], accA[4 * c + 1], accA[4 * c + 2], accA[4 * c + 3]};
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            f32x4 *dp = (f32x4 *)(slots + (w * 2 + 1) * SLOT_FLOATS) + lane;
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                dp[c * 64] = f32x4{accB[4 * c + 0], accB[4 * c + 1], accB[4 * c + 2], accB[4 * c + 3]};
+        }
+        if (DBG & 1) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); st3 = __builtin_amdgcn_s_memtime(); }
+        // stage barrier: only the LDS traffic has to be complete, not the pv / spike stores of the epilogue
+        lds_barrier();
+        if (DBG & 1) {
+            const unsigned long long st4 = __builtin_amdgcn_s_memtime();
+            dbg[0] += st1 - st0; dbg[1] += st2 - st1; dbg[2] += st3 - st2; dbg[3] += st4 - st3;
+        }
+    };
+
+    const int nstage = 8 * NP + 8;
+    for (int g = 0; g < nstage; ++g) {
+        switch ((g - w) & 7) {      // wave-uniform
+        case 0: stage(g, std::integral_constant<int, 0>{}); break;
+        case 1: stage(g, std::integral_constant<int, 1>{}); break;
+        case 2: stage(g, std::integral_constant<int, 2>{}); break;
+        case 3: stage(g, std::integral_constant<int, 3>{}); break;
+        case 4: stage(g, std::integral_constant<int, 4>{}); break;
+        case 5: stage(g, std::integral_constant<int, 5>{}); break;
+        case 6: stage(g, std::integral_constant<int, 6>{}); break;
+        default: stage(g, std::integral_constant<int, 7>{}); break;
+        }
+    }
+
+    if ((DBG & 1) && lane == 0 && b == 0) {
+        unsigned long long *dp = (unsigned long long *)v_out + w * 8;       // v_out doubles as the debug buffer
+        dp[0] = __builtin_amdgcn_s_memtime() - dbg_t0;
+        dp[1] = dbg[0]; dp[2] = dbg[1]; dp[3] = dbg[2]; dp[4] = dbg[3];
+    }
+    // state back to HBM: eps1 of the last step T - 1 lives in the "t+1" image
+    static_for<0, 8>([&](auto SC) {
+        constexpr int S = decltype(SC)::value, M = tp_trace_m(S);
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const long gidx = (b * 32 + 4 * w + 2 * e + h) * 256 + 32 * M + j;
+            eps0_g[gidx] = e0[S][e];
+            eps1_g[gidx] = lds[TP_IMGP + toff + e * 2 * CHF + 2 * M * ROWF];
+        }
+    });
+    if (REFRACTORY) {
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+            const int re = (rowpk >> (4 * ((s + w) & 7))) & 15;
+#pragma unroll
+            for (int k = 0; k < 2; ++k) arp_g[(b * 32 + ech + k) * 256 + re * 16 + px] = arp[s][k];
+        }
     }
 }
 
@@ -3526,26 +3899,27 @@ static int dcll_conv_lif_sequence_run(const dcll_conv_desc *d, const uint32_t *s
         return dcll_launch_seq_c32t(d, spk_in, W, b, tau4, eps0, eps1, arp, spk_out, pv_out, v_out, state_scratch, T, B, st);
     }
     if (n_ro == 0 && T >= DCLL_C32D_MIN_T) {      // long sequence: two tiles per wave and stage
-#define DCLL_LAUNCH_C32D(R, O)                                                                                          \
-    hipLaunchKernelGGL((k_lif_seq_c32d<R, O>), dim3(B), dim3(512), 0, st, spk_in, W, b, tau4, eps0, eps1, arp, spk_out, \
-                       pv_out, v_out, T, B, d->alpharp, d->wrp)
-        if (d->refractory) {
-            switch (out) {
-            case 0: DCLL_LAUNCH_C32D(true, 0); break;
-            case 1: DCLL_LAUNCH_C32D(true, 1); break;
-            case 2: DCLL_LAUNCH_C32D(true, 2); break;
-            default: DCLL_LAUNCH_C32D(true, 3); break;
-            }
+        // even T: a tile is one image row at two timesteps (k_lif_seq_c32d); odd T: two image rows at one (k_lif_seq_c32rp)
+        const bool tp = (T & 1) == 0;
+#define DCLL_LAUNCH_C32D(K, R, O)                                                                                       \
+    hipLaunchKernelGGL((K<R, O>), dim3(B), dim3(512), 0, st, spk_in, W, b, tau4, eps0, eps1, arp, spk_out, pv_out,      \
+                       v_out, T, B, d->alpharp, d->wrp)
+#define DCLL_LAUNCH_C32D_O(K, R)                                                                                        \
+    switch (out) {                                                                                                     \
+    case 0: DCLL_LAUNCH_C32D(K, R, 0); break;                                                                          \
+    case 1: DCLL_LAUNCH_C32D(K, R, 1); break;                                                                          \
+    case 2: DCLL_LAUNCH_C32D(K, R, 2); break;                                                                          \
+    default: DCLL_LAUNCH_C32D(K, R, 3); break;                                                                         \
+    }
+        if (tp) {
+            if (d->refractory) { DCLL_LAUNCH_C32D_O(k_lif_seq_c32d, true) } else { DCLL_LAUNCH_C32D_O(k_lif_seq_c32d, false) }
+            HIP_CHECK_LAUNCH("k_lif_seq_c32d");
         } else {
-            switch (out) {
-            case 0: DCLL_LAUNCH_C32D(false, 0); break;
-            case 1: DCLL_LAUNCH_C32D(false, 1); break;
-            case 2: DCLL_LAUNCH_C32D(false, 2); break;
-            default: DCLL_LAUNCH_C32D(false, 3); break;
-            }
+            if (d->refractory) { DCLL_LAUNCH_C32D_O(k_lif_seq_c32rp, true) } else { DCLL_LAUNCH_C32D_O(k_lif_seq_c32rp, false) }
+            HIP_CHECK_LAUNCH("k_lif_seq_c32rp");
         }
+#undef DCLL_LAUNCH_C32D_O
 #undef DCLL_LAUNCH_C32D
-        HIP_CHECK_LAUNCH("k_lif_seq_c32d");
         return DCLL_OK;
     }
 #define DCLL_ARGS out, B, st, spk_in, W, b, tau4, eps0, eps1, arp, spk_out, pv_out, v_out, ro_Wp, ro_b, ro_out, T, d->alpharp, d->wrp
