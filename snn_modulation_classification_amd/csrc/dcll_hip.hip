@@ -4001,7 +4001,7 @@ static int launch_c1(const dcll_conv_desc *d, const int32_t *cells, const float 
         return dcll_launch_seq_c1t(d, cells, iq, thr_i, thr_q, tail, L, t0, W, b, tau4, eps0, eps1, arp, spk_out, pv_out, v_out,
                                    state_scratch, T, B, st, presig);
     const bool fastpath = d->c_out == 32 && spk_out && pv_out && !v_out;
-    if (presig && !fastpath) { v_out = pv_out; pv_out = nullptr; }
+    if (presig && pv_out && !fastpath) { v_out = pv_out; pv_out = nullptr; }     // (no pv wanted: v_out stays the caller's)
 #define DCLL_LAUNCH_C1(R, F, Q)                                                                                         \
     hipLaunchKernelGGL((k_lif_seq_c1<R, F, Q>), dim3(B), dim3(256), 0, st, d->c_out, cells, iq, thr_i, thr_q, tail, L, t0, W,  \
                        b, tau4, eps0, eps1, arp, spk_out, pv_out, v_out, T, B, d->alpharp, d->wrp)

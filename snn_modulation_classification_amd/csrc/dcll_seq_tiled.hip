@@ -528,7 +528,8 @@ int dcll_launch_seq_c1t(const dcll_conv_desc *d, const int32_t *cells, const flo
     if (rc) return rc;
     const float *eps0_in = state_scratch, *eps1_in = state_scratch + nstate;
     const bool fastpath = d->c_out == 32 && spk_out && pv_out && !v_out && (long)d->h * d->w * 32 < (1L << 30);
-    if (presig && !fastpath) { v_out = pv_out; pv_out = nullptr; }        // (the caller made sure only one of them is wanted)
+    // (the caller made sure that at most one of them is wanted; no pv wanted: v_out stays the caller's)
+    if (presig && pv_out && !fastpath) { v_out = pv_out; pv_out = nullptr; }
 #define DCLL_LAUNCH_C1T(R, F)                                                                                           \
     hipLaunchKernelGGL((k_lif_seq_c1t<R, F>), dim3((unsigned)nwg), dim3(256), 0, st, d->c_out, cells, iq, thr_i, thr_q,  \
                        tail, L, t0, W, b, tau4, eps0_in, eps1_in, eps0, eps1, arp, spk_out, pv_out, v_out, T, B, d->h, d->w,         \
