@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DCLL_ABI_VERSION 7
+#define DCLL_ABI_VERSION 8
 
 enum {
     DCLL_OK = 0,
@@ -491,6 +491,45 @@ int dcll_iq_encode(const float *iq, const float *thr_i, const float *thr_q, cons
 /* Unpack (T*B, C, HW/32) packed spikes to fp32 (T*B, C, HW) and back — glue for the tensor-level API. */
 int dcll_unpack_spikes(const uint32_t *packed, float *dense, int64_t nwords, void *stream);
 int dcll_pack_spikes(const float *dense, uint32_t *packed, int64_t nwords, void *stream);
+
+/*
+ * ABI 8 — all T timesteps of ANY plain conv layer in one launch (k_lif_seq_any, one workgroup per sample, the neuron state in
+ * LDS): the fused path of the layers the geometry-specialised calls above refuse — networks/mnist_conv.yaml (28x28, 7x7, pad 2,
+ * pooling 2 / 1 / 2, 16 / 24 / 32 channels), radio_ml_conv.yaml on planes such as 24x24 or 12x32.  Additions only: the calls
+ * above, their refusals and their kernels are unchanged.
+ * Served (else DCLL_ERR_UNSUPPORTED, before any launch): stride = dilation = groups = 1; any c_in; c_out <= 32; kh, kw <= 16;
+ * any padding (the conv plane may shrink or grow); any pooling >= 1 (MaxPool2d(kernel = stride = pool, padding (pool-1)/2),
+ * floor mode); time constants constant over (h, w) per input channel; and a per-sample state that one workgroup holds on chip:
+ *   LDS form       4 bytes x (c_in (h + 2 pad_h)(w + 2 pad_w) [zero-padded eps1] + c_in h w [eps0] + c_out ch cw [v of one step]
+ *                  + c_out ch cw [arp, refractory layers only] + 4 c_in + 32) <= 160 KiB, the LDS of a workgroup; or, beyond that,
+ *   register form  layers WITHOUT pooling with c_in h w <= 18432 and ch cw <= 768 (radio_ml_conv.yaml's 32 -> 32 layers on 24x24
+ *                  or 12x32): eps0 and arp live in registers, LDS holds 4 bytes x (c_in (h + 2 pad_h)(w + 2 pad_w) + 4 c_in + 32).
+ * dcll_conv_lif_sequence_any_lds returns the LDS bytes of the form that serves the layer (the weights the kernel keeps behind
+ * them where there is room are not counted), or 0 for a descriptor that is not served (invalid ones included).
+ * Spike planes cross this call as ceil(hw / 32) words per (t, b, channel) plane: bit pix % 32 of word pix / 32, tail bits zero
+ * (identical to the format above whenever hw % 32 == 0); dcll_pack_spike_planes / dcll_unpack_spike_planes convert n_planes
+ * dense fp32 planes of hw values (non-zero = spike) to and from it.
+ *   spk_in   (T,B,c_in,ceil(h*w/32)) uint32      tau4 (4,c_in) as above      b (c_out), or NULL: the chains start at 0
+ *   eps0,eps1 (B,c_in,h,w), arp (B,c_out,ch,cw)  neuron state in/out (read at t = 0, written after t = T-1); arp may be NULL
+ *                                                 for a layer that is not refractory
+ *   spk_out  (T,B,c_out,ceil(ph*pw/32)) uint32   POOLED spikes = pooled v > 0; may be NULL
+ *   pv_out   (T,B,c_out,ph,pw)                   sigmoid(pooled v); may be NULL
+ *   v_out    (T,B,c_out,ch,cw)                   un-pooled v = pvmem (+ arp'), for tests; may be NULL
+ *   w_scratch  dcll_conv_lif_sequence_any_scratch(d) floats: the weights in MFMA fragment order, written by a small kernel in
+ *              front of the layer kernel on every call (the caller may reuse it once the call's work has run)
+ * Arithmetic: the contract at the top of this file — every v is ONE fmaf chain from b[co] over (cp, ky, kx, h) on
+ * v_mfma_f32_32x32x2_f32, two consecutive links per instruction; the unpaired last channel of an odd c_in runs its taps two by
+ * two, and a chain of odd length ends with fmaf(0, 0, acc) (== acc, except that -0.0 becomes +0.0).  v, the spikes and the
+ * final state are bit-identical to T calls of dcll_conv_lif_step; pv to the sigmoid's last ulp.
+ * T == 0 or B == 0: DCLL_OK, nothing is looked at.  fp32 weights only (no dcll_layer_opts here).
+ */
+int64_t dcll_conv_lif_sequence_any_lds(const dcll_conv_desc *d);
+int64_t dcll_conv_lif_sequence_any_scratch(const dcll_conv_desc *d);
+int dcll_conv_lif_sequence_any(const dcll_conv_desc *d, const uint32_t *spk_in, const float *W, const float *b,
+                               const float *tau4, float *eps0, float *eps1, float *arp, uint32_t *spk_out, float *pv_out,
+                               float *v_out, float *w_scratch, int32_t T, int32_t B, void *stream);
+int dcll_pack_spike_planes(const float *dense, uint32_t *packed, int64_t n_planes, int32_t hw, void *stream);
+int dcll_unpack_spike_planes(const uint32_t *packed, float *dense, int64_t n_planes, int32_t hw, void *stream);
 
 #ifdef __cplusplus
 }

@@ -93,35 +93,7 @@ static inline int split16_max_batch(void)
     return e && *e ? atoi(e) : 256;
 }
 
-static inline void conv_shape(const dcll_conv_desc *d, int *ch, int *cw, int *ph, int *pw)
-{
-    // (reference get_output_shape, dcll/pytorch_libdcll.py:368-375; stride = dilation = 1: h + 2 pad - kh + 1)
-    *ch = (d->h + 2 * d->pad_h - d->dilation * (d->kh - 1) - 1) / d->stride + 1;
-    *cw = (d->w + 2 * d->pad_w - d->dilation * (d->kw - 1) - 1) / d->stride + 1;
-    *ph = (*ch + 2 * ((d->pool_h - 1) / 2) - d->pool_h) / d->pool_h + 1;
-    *pw = (*cw + 2 * ((d->pool_w - 1) / 2) - d->pool_w) / d->pool_w + 1;
-}
-
-// the specialised kernels (MFMA step / sequence / weight-gradient kernels, the tiled VALU kernel) are plain convolutions
-static inline bool plain_conv(const dcll_conv_desc *d) { return d->stride == 1 && d->dilation == 1 && d->groups == 1; }
-
-static int check_desc(const dcll_conv_desc *d)
-{
-    if (!d) return fail(DCLL_ERR_INVALID, "null descriptor");
-    if (d->c_in < 1 || d->c_out < 1 || d->h < 1 || d->w < 1 || d->kh < 1 || d->kw < 1 || d->pad_h < 0 ||
-        d->pad_w < 0 || d->pool_h < 1 || d->pool_w < 1 || d->target < 0)
-        return fail(DCLL_ERR_INVALID, "descriptor has a non-positive dimension");
-    // stride / dilation / groups other than 1 (F.conv2d's, reference :417 / :495): served by the generic per-step kernels
-    // (k_conv_lif, k_bwd_wgrad) only — ConvNetwork never builds such a layer
-    if (d->stride < 1 || d->dilation < 1 || d->groups < 1 || d->c_in % d->groups != 0 || d->c_out % d->groups != 0)
-        return fail(DCLL_ERR_INVALID, "stride / dilation / groups must be >= 1 and groups must divide c_in and c_out");
-    if (d->h + 2 * d->pad_h < d->dilation * (d->kh - 1) + 1 || d->w + 2 * d->pad_w < d->dilation * (d->kw - 1) + 1)
-        return fail(DCLL_ERR_INVALID, "empty conv/pool output");
-    int ch, cw, ph, pw;
-    conv_shape(d, &ch, &cw, &ph, &pw);
-    if (ch < 1 || cw < 1 || ph < 1 || pw < 1) return fail(DCLL_ERR_INVALID, "empty conv/pool output");
-    return DCLL_OK;
-}
+// conv_shape / plain_conv / check_desc: dcll_internal.h (shared with dcll_seq_any.hip)
 
 extern "C" int dcll_conv_out_shape(const dcll_conv_desc *d, int32_t *ch, int32_t *cw, int32_t *ph, int32_t *pw)
 {

@@ -33,6 +33,37 @@ static inline int fail(int code, const char *msg, const char *who = nullptr)
     return code;
 }
 
+// descriptor geometry and checks shared by the entry points of every translation unit
+static inline void conv_shape(const dcll_conv_desc *d, int *ch, int *cw, int *ph, int *pw)
+{
+    // (reference get_output_shape, dcll/pytorch_libdcll.py:368-375; stride = dilation = 1: h + 2 pad - kh + 1)
+    *ch = (d->h + 2 * d->pad_h - d->dilation * (d->kh - 1) - 1) / d->stride + 1;
+    *cw = (d->w + 2 * d->pad_w - d->dilation * (d->kw - 1) - 1) / d->stride + 1;
+    *ph = (*ch + 2 * ((d->pool_h - 1) / 2) - d->pool_h) / d->pool_h + 1;
+    *pw = (*cw + 2 * ((d->pool_w - 1) / 2) - d->pool_w) / d->pool_w + 1;
+}
+
+// the specialised kernels (MFMA step / sequence / weight-gradient kernels, the tiled VALU kernel) are plain convolutions
+static inline bool plain_conv(const dcll_conv_desc *d) { return d->stride == 1 && d->dilation == 1 && d->groups == 1; }
+
+static inline int check_desc(const dcll_conv_desc *d)
+{
+    if (!d) return fail(DCLL_ERR_INVALID, "null descriptor");
+    if (d->c_in < 1 || d->c_out < 1 || d->h < 1 || d->w < 1 || d->kh < 1 || d->kw < 1 || d->pad_h < 0 ||
+        d->pad_w < 0 || d->pool_h < 1 || d->pool_w < 1 || d->target < 0)
+        return fail(DCLL_ERR_INVALID, "descriptor has a non-positive dimension");
+    // stride / dilation / groups other than 1 (F.conv2d's, reference :417 / :495): served by the generic per-step kernels
+    // (k_conv_lif, k_bwd_wgrad) only — ConvNetwork never builds such a layer
+    if (d->stride < 1 || d->dilation < 1 || d->groups < 1 || d->c_in % d->groups != 0 || d->c_out % d->groups != 0)
+        return fail(DCLL_ERR_INVALID, "stride / dilation / groups must be >= 1 and groups must divide c_in and c_out");
+    if (d->h + 2 * d->pad_h < d->dilation * (d->kh - 1) + 1 || d->w + 2 * d->pad_w < d->dilation * (d->kw - 1) + 1)
+        return fail(DCLL_ERR_INVALID, "empty conv/pool output");
+    int ch, cw, ph, pw;
+    conv_shape(d, &ch, &cw, &ph, &pw);
+    if (ch < 1 || cw < 1 || ph < 1 || pw < 1) return fail(DCLL_ERR_INVALID, "empty conv/pool output");
+    return DCLL_OK;
+}
+
 // dcll_kernel_trace (ABI 5): while a thread records, every launch check notes the kernel's name (dcll_hip.hip)
 __attribute__((visibility("hidden"))) void dcll_trace_note(const char *name);
 

@@ -842,3 +842,106 @@ class ConvNetwork(torch.nn.Module):
         if batch_slice is not None and 'o' in res:
             res['o'] = res['o'].clone()
         return res
+
+    # -- the fused path of any plain conv network (k_lif_seq_any, ABI 8): opt-in, beside test_sequence ---------------------
+    def sequence_any_supported(self):
+        """True if every layer is served by dcll_conv_lif_sequence_any (Conv2dDCLLlayer.sequence_any_supported): any plain
+        conv spec with at most 32 output channels per layer whose per-sample working set fits a workgroup's LDS —
+        mnist_conv.yaml, radio_ml_conv.yaml on any small plane.  Independent of sequence_supported()."""
+        return all(isinstance(s.dclllayer, Conv2dDCLLlayer) and s.dclllayer.sequence_any_supported()
+                   for s in self.dcll_slices)
+
+    def _any_input_planes(self, x):
+        """The first layer's input of one chunk as packed spike planes (T,B,C,ceil(H*W/32)) int32: cell indices (T,B)
+        through dcll_cells_to_planes, dense planes (T,B,C,H,W) of any float / bool dtype through the packer, a packed int32
+        tensor as it is."""
+        L = self.dcll_slices[0].dclllayer
+        (H, W), C = L.im_dims, L.in_channels
+        words = (H * W + 31) // 32
+        if x.dim() == 2:
+            if C != 1:
+                raise ValueError('cell indices (T,B) describe a one-channel input, the first layer has %d' % C)
+            planes = ops.cells_to_planes(x.to(torch.int32).contiguous(), H * W)
+            return ops.pack_spike_planes(planes).reshape(x.shape[0], x.shape[1], 1, words)
+        if x.dtype == torch.int32:
+            if tuple(x.shape[2:]) != (C, words):
+                raise ValueError('packed input must be (T,B,%d,%d) int32, got %s' % (C, words, tuple(x.shape)))
+            return x.contiguous()
+        if tuple(x.shape[2:]) != (C, H, W):
+            raise ValueError('dense input must be (T,B,%d,%d,%d), got %s' % (C, H, W, tuple(x.shape)))
+        T, B = x.shape[:2]
+        return ops.pack_spike_planes(x.to(torch.float32).reshape(T, B, C, H * W))
+
+    @torch.no_grad()
+    def test_sequence_any(self, x, collect=True, keep_spikes=False):
+        """Equivalent of `for t in range(T): net.test(x[t])` on the fused kernel of ANY plain conv layer (k_lif_seq_any):
+        x = dense spike planes (T,B,C,H,W) on the device (any float or bool dtype; packed on the device), the same planes
+        already packed ((T,B,C,ceil(H*W/32)) int32), or cell indices (T,B) for a one-channel first layer.  Every layer runs
+        all T steps in one launch, the readouts as one GEMM over the T x B rows, then the per-step argmax and the vote;
+        slices that collect statistics get the pv counts of the histogram steps.  Fills every slice's `clout` (collect) and
+        returns test_sequence's dict: 'logits', 'clout', 'vote', 'lowhigh' per layer, 'o', and 'spikes' with keep_spikes
+        (per layer (T,B,C,ceil(ph*pw/32)) int32).  Batches are chunked under DCLL_PV_BUDGET_GB like test_sequence."""
+        if not self.sequence_any_supported():
+            raise ops._lib.DCLLUnsupported('dcll_conv_lif_sequence_any does not serve every layer of this network; '
+                                           'use net.test(x[t])')
+        T, B = int(x.shape[0]), int(x.shape[1])
+        dev = x.device
+        per_sample = 4 * T * max(s.dclllayer.out_channels * int(np.prod(s.dclllayer.output_shape)) for s in self.dcll_slices)
+        chunk = max(1, min(B, int(self.pv_budget_bytes // max(per_sample, 1))))
+        if chunk < B and dev.type == 'cuda':
+            ncu = torch.cuda.get_device_properties(dev).multi_processor_count      # one workgroup per sample
+            if chunk >= ncu:
+                chunk -= chunk % ncu
+        if chunk < B:
+            for s in self.dcll_slices:
+                if s.dclllayer.i2h.state is None or s.dclllayer.i2h.state.eps0.shape[0] != B:
+                    s.dclllayer.i2h.init_state(B, s.dclllayer.im_dims)
+            parts = [self._sequence_any_chunk(x[:, b0:min(B, b0 + chunk)], T, min(B, b0 + chunk) - b0, b0, keep_spikes)
+                     for b0 in range(0, B, chunk)]
+            cat = lambda key, dim: [None if parts[0][key][i] is None else torch.cat([p[key][i] for p in parts], dim)
+                                    for i in range(self.num_layers)]
+            res = dict(logits=cat('logits', 1), clout=cat('clout', 1), vote=cat('vote', 0),
+                       lowhigh=[None if parts[0]['lowhigh'][i] is None else sum(p['lowhigh'][i] for p in parts)
+                                for i in range(self.num_layers)], o=torch.cat([p['o'] for p in parts], 1))
+            if keep_spikes:
+                res['spikes'] = cat('spikes', 1)
+        else:
+            res = self._sequence_any_chunk(x, T, B, None, keep_spikes)
+        if collect:
+            for i, s in enumerate(self.dcll_slices):
+                L = s.dclllayer
+                s.set_sequence_result(res['clout'][i], T, lowhigh=res['lowhigh'][i],
+                                      numel=B * L.out_channels * int(np.prod(L.output_shape)), vote=res['vote'][i])
+        return res
+
+    def _sequence_any_chunk(self, x, T, B, batch_slice, keep_spikes):
+        """All layers over all T steps for B samples (the whole batch, or rows batch_slice.. of every layer's state)."""
+        for s in self.dcll_slices:
+            i2h = s.dclllayer.i2h
+            if batch_slice is None and (i2h.state is None or i2h.state.eps0.shape[0] != B):
+                i2h.init_state(B, s.dclllayer.im_dims)
+        cur = self._any_input_planes(x)
+        scratch = self.__dict__.setdefault('_any_scratch', {})     # per layer: the permuted weights of its launch
+        res = dict(logits=[], clout=[], vote=[], lowhigh=[])
+        if keep_spikes:
+            res['spikes'] = []
+        for i, s in enumerate(self.dcll_slices):
+            L = s.dclllayer
+            last = (i == self.num_layers - 1)
+            spk, pv, _ = L.forward_sequence_any(cur, T, B, want_spikes=(not last) or keep_spikes, want_pv=True,
+                                                buffers=scratch.setdefault(i, {}), batch_slice=batch_slice)
+            res['lowhigh'].append(ops.pv_lowhigh(pv.reshape(T, -1), T, s.iter) if s.collect_stats else None)
+            if keep_spikes:
+                res['spikes'].append(spk)
+            Wt, bias = L.stacked_readout()
+            ro = ops.readout(pv.reshape(T * B, -1), Wt, bias).reshape(T, B, -1)
+            p = ro[..., :self.target_size]
+            logits = p
+            if last:
+                logits = res['o'] = ro[..., self.target_size:]
+            clout, vote = ops.argmax_vote(logits.contiguous())
+            res['logits'].append(p)
+            res['clout'].append(clout)
+            res['vote'].append(vote)
+            cur = spk
+        return res

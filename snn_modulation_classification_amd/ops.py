@@ -743,6 +743,74 @@ def pack_spikes(dense):
     return packed
 
 
+def pack_spike_planes(dense):
+    """(..., hw) float32 planes of any size -> (..., ceil(hw/32)) int32: bit pix % 32 of word pix / 32, tail bits zero
+    (dcll_pack_spike_planes; the format of conv_lif_sequence_any — pack_spikes' whenever hw % 32 == 0)."""
+    _expect(dense, "dense", torch.float32)
+    dense = dense.contiguous()
+    hw = int(dense.shape[-1])
+    packed = torch.empty(dense.shape[:-1] + ((hw + 31) // 32,), device=dense.device, dtype=torch.int32)
+    check(_lib.get().dcll_pack_spike_planes(ptr(dense), ptr(packed), dense.numel() // max(hw, 1), hw, stream_ptr()),
+          "dcll_pack_spike_planes")
+    return packed
+
+
+def unpack_spike_planes(packed, hw):
+    """(..., ceil(hw/32)) int32 -> (..., hw) float32 (dcll_unpack_spike_planes)."""
+    _expect(packed, "packed", torch.int32)
+    packed = packed.contiguous()
+    hw = int(hw)
+    if packed.shape[-1] != (hw + 31) // 32:
+        raise ValueError("unpack_spike_planes: %d words per plane do not hold %d pixels" % (packed.shape[-1], hw))
+    dense = torch.empty(packed.shape[:-1] + (hw,), device=packed.device, dtype=torch.float32)
+    check(_lib.get().dcll_unpack_spike_planes(ptr(packed), ptr(dense), dense.numel() // max(hw, 1), hw, stream_ptr()),
+          "dcll_unpack_spike_planes")
+    return dense
+
+
+def sequence_any_lds(desc):
+    """LDS bytes k_lif_seq_any needs per sample of this layer, 0 = the layer is not served (dcll_conv_lif_sequence_any_lds;
+    host-only: no device is touched)."""
+    return int(_lib.get().dcll_conv_lif_sequence_any_lds(ctypes.byref(desc)))
+
+
+def sequence_any_supported(desc):
+    """True if dcll_conv_lif_sequence_any serves the layer: a plain conv with c_out <= 32, a kernel up to 16x16 and a
+    per-sample working set within a workgroup's LDS (include/dcll_hip.h, ABI 8)."""
+    return sequence_any_lds(desc) > 0
+
+
+def conv_lif_sequence_any(desc, spk_in, W, b, tau4, eps0, eps1, arp, T, B, want_spikes=True, want_pv=True, want_v=False,
+                          out=None):
+    """All T steps of any plain conv layer in one launch (k_lif_seq_any).  spk_in (T,B,c_in,ceil(h*w/32)) int32 spike
+    planes (pack_spike_planes) -> (pooled spikes (T,B,c_out,ceil(ph*pw/32)) int32, pv (T,B,c_out,ph,pw), v (T,B,c_out,ch,cw)),
+    each None when not wanted.  `out`: optional dict of reusable buffers 'spk' / 'pv' / 'w_scratch'."""
+    dev = W.device
+    out = {} if out is None else out
+    ch, cw, ph, pw = conv_out_shape(desc)
+    iw, ow = (desc.h * desc.w + 31) // 32, (ph * pw + 31) // 32
+    _expect(spk_in, "spk_in", torch.int32, (T, B, desc.c_in, iw))
+    _check_layer_operands(desc, W, b, eps0, eps1, arp, B, tau4=tau4)
+    spk = out.get("spk") if want_spikes else None
+    if want_spikes and spk is None:
+        spk = torch.empty((T, B, desc.c_out, ow), device=dev, dtype=torch.int32)
+    pv = out.get("pv") if want_pv else None
+    if want_pv and pv is None:
+        pv = torch.empty((T, B, desc.c_out, ph, pw), device=dev, dtype=torch.float32)
+    _expect(spk, "spk_out", torch.int32, (T, B, desc.c_out, ow))
+    _expect(pv, "pv_out", torch.float32, (T, B, desc.c_out, ph, pw))
+    v = torch.empty((T, B, desc.c_out, ch, cw), device=dev, dtype=torch.float32) if want_v else None
+    n = int(_lib.get().dcll_conv_lif_sequence_any_scratch(ctypes.byref(desc)))
+    scratch = out.get("w_scratch")
+    if scratch is None or scratch.numel() < n or scratch.device != dev:
+        scratch = out["w_scratch"] = torch.empty((n,), device=dev, dtype=torch.float32)
+    _expect(scratch, "w_scratch", torch.float32)
+    rc = _lib.get().dcll_conv_lif_sequence_any(ctypes.byref(desc), ptr(spk_in), ptr(W), ptr(b), ptr(tau4), ptr(eps0), ptr(eps1),
+                                               ptr(arp), ptr(spk), ptr(pv), ptr(v), ptr(scratch), T, B, stream_ptr())
+    check(rc, "dcll_conv_lif_sequence_any")
+    return spk, pv, v
+
+
 LOSS_KINDS = {"SmoothL1Loss": _lib.LOSS_SMOOTH_L1, "MSELoss": _lib.LOSS_MSE}
 
 

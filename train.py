@@ -74,6 +74,10 @@ def parse_args(argv=None):
     p.add_argument('--host_encoding', action='store_true',
                    help='encode the training batches with the host iq2spiketrain loop (the reference\'s way) instead of on '
                         'the device')
+    p.add_argument('--any_sequence_path', action='store_true',
+                   help='opt in: the test phase of a network without a geometry-specialised sequence kernel '
+                        '(sequence_supported() False, e.g. --data MNIST with mnist_conv.yaml, or RadioML on a 24x24 plane) runs '
+                        'ConvNetwork.test_sequence_any (k_lif_seq_any) where it serves every layer, instead of net.test per timestep')
     p.add_argument('--gpus', type=int, default=1, metavar='N',
                    help='ranks (one process per GPU): every batch is sharded over them, the local-learning gradients are '
                         'averaged over the ranks every timestep (one bucketed all-reduce)')
@@ -163,10 +167,29 @@ def main(argv=None):
     import time
     t_train, n_train = 0.0, 0
 
+    # --any_sequence_path: a network without a specialised sequence kernel is tested on k_lif_seq_any (one process only; several
+    # ranks keep evaluate_batch's sharded per-step evaluation)
+    use_any = args.any_sequence_path and not use_sequence and world == 1 and net.sequence_any_supported()
+
+    def evaluate_batch_any(samples, labels1h):
+        """The per-step branch of evaluate_batch (host-encoded planes, reference test_radio_ml.py:142-146) with its T-loop replaced
+        by ConvNetwork.test_sequence_any on the same planes -> per-layer accuracies."""
+        T = args.n_iters_test
+        spikes, targets = iq2spiketrain(samples, labels1h, out_w=args.I_resolution, out_h=args.Q_resolution,
+                                        min_I=args.I_bounds[0], max_I=args.I_bounds[1], min_Q=args.Q_bounds[0],
+                                        max_Q=args.Q_bounds[1], max_duration=T)
+        net.reset()
+        net.eval()
+        net.test_sequence_any(torch.Tensor(spikes).to(pytorch_libdcll.device)[:T])
+        return net.accuracy(torch.as_tensor(np.asarray(targets), dtype=torch.float32))
+
     def run_tests(step):
         net.batch_size = max(1, np.diff(parallel.shard_range(args.batch_size_test, rank, world))[0])
         acc = np.empty([len(test_batches), len(net.dcll_slices)])
         for i, (samples, labels) in enumerate(test_batches):
+            if use_any:
+                acc[i, :] = evaluate_batch_any(samples, to_one_hot(labels, target_size))
+                continue
             acc[i, :], _ = evaluation.evaluate_batch(net, args, samples, to_one_hot(labels, target_size), encoder,
                                                      use_sequence)
         net.batch_size = max(1, np.diff(parallel.shard_range(args.batch_size, rank, world))[0])
@@ -331,8 +354,11 @@ def main_mnist(args):
                 tx, ty = spikes_of(ts, tl, st_test)
                 net.reset()
                 net.eval()
-                for t in range(args.n_iters_test):
-                    net.test(x=tx[t])
+                if args.any_sequence_path and not net.sequence_supported() and net.sequence_any_supported():
+                    net.test_sequence_any(tx[:args.n_iters_test])
+                else:
+                    for t in range(args.n_iters_test):
+                        net.test(x=tx[t])
                 acc_test[step // args.n_test_interval, i, :] = net.accuracy(ty)
             print('[TEST]  Step {} \t Accuracy {} \t Ref N/A'.format(
                 str(step).zfill(5), np.mean(acc_test[step // args.n_test_interval], axis=0)))
