@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DCLL_ABI_VERSION 8
+#define DCLL_ABI_VERSION 9
 
 enum {
     DCLL_OK = 0,
@@ -57,7 +57,8 @@ typedef struct dcll_conv_desc {
                                        * the sequence calls return DCLL_ERR_UNSUPPORTED for them.  The backward calls serve
                                        * kernels of up to 64 taps (kh * kw <= 64) whose padded input row fits the LDS-staged
                                        * weight gradient (about (w + 2 pad_w) * ((kh - 1) dilation + 1) <= 12 000 floats) and
-                                       * return DCLL_ERR_UNSUPPORTED beyond — F.conv2d itself has no such limit            */
+                                       * return DCLL_ERR_UNSUPPORTED beyond — F.conv2d itself has no such limit.  (Plain convs
+                                       * beyond those limits: dcll_conv_lif_backward_any, ABI 9, below.)                  */
     int32_t pool_h, pool_w;     /* MaxPool2d(kernel=stride=pool, padding=(pool-1)/2)   :542-549          */
     int32_t target;             /* target_size: rows of i2o.weight (and output_.weight)                  */
     int32_t output_layer;       /* !=0: also o = output_(flatten(pv))  :605-606                          */
@@ -530,6 +531,38 @@ int dcll_conv_lif_sequence_any(const dcll_conv_desc *d, const uint32_t *spk_in, 
                                float *v_out, float *w_scratch, int32_t T, int32_t B, void *stream);
 int dcll_pack_spike_planes(const float *dense, uint32_t *packed, int64_t n_planes, int32_t hw, void *stream);
 int dcll_unpack_spike_planes(const uint32_t *packed, float *dense, int64_t n_planes, int32_t hw, void *stream);
+
+/*
+ * ABI 9 — the backward of one layer step with the weight gradient of ANY plain conv layer on fp32-MFMA tiles (k_bwd_wgrad_any):
+ * dcll_conv_lif_backward / dcll_conv_lif_backward_open with the same arguments, results and scratch rule (B c_out ch cw +
+ * k (c_out (c_in kh kw + 1)) floats, k >= 1; less: DCLL_ERR_INVALID), for the layers whose weight gradient the calls above
+ * compute on the generic VALU kernel or refuse (more than 64 taps, rows too wide).  Additions only: the calls above, their
+ * kernels, launch logs and refusals are unchanged; dv, the fixed-order reduction and the output_ gradient are the same kernels.
+ * Served (else DCLL_ERR_UNSUPPORTED, before any launch): stride = dilation = groups = 1; any c_in; c_out <= 32; kh, kw <= 16;
+ * any padding, pooling and batch; and a smallest working set that fits the 160 KiB of LDS of a workgroup:
+ *   4 bytes x (cg (h + 2 pad_h)(w + 2 pad_w) + 1 [zero-padded eps1 of the cg input channels that 32 consecutive weight columns
+ *   touch] + c_out (ch (cw rounded up to even) | 1) [the sample's dv plane]).
+ * dW[co][n] = sum_{b,pix} g[b,co,pix] E[b][n][pix], n = ci kh kw + tap, as a GEMM on v_mfma_f32_32x32x2_f32 (M = c_out padded to
+ * 32, N = columns in tiles of 32, one MFMA per pixel pair of a row; an odd row's last pixel is paired with a zero).  A workgroup
+ * owns up to 32 consecutive column tiles of one batch chunk — fewer where LDS or a small batch ask for it ("column split");
+ * with fewer than five tiles its waves split the pixels and add their pieces in wave order ("pixel split").  The launch log
+ * names the form, NQ = accumulator tiles per wave (1, 2, 4): "k_bwd_wgrad_any<NQ>", "k_bwd_wgrad_any<NQ> (column split)",
+ * "k_bwd_wgrad_any<1> (pixel split)" or "k_bwd_wgrad_any<1> (column split, pixel split)".  A small batch lowers the tiles per
+ * workgroup only to layouts that need no more LDS than the full launch.
+ * At most 256 batch chunks (partial rows part[chunk][co][c_in kh kw + 1]); every sum has a fixed order: two runs give the same
+ * bits, and _any_open + dcll_grad_reduce_adam gives _any's bits.  Not bit-identical to dcll_conv_lif_backward (another order).
+ * dcll_conv_lif_backward_any_lds returns the LDS bytes per workgroup of a full launch (no launch uses more), or 0 for a
+ * descriptor that is not served (invalid ones included).
+ */
+int64_t dcll_conv_lif_backward_any_lds(const dcll_conv_desc *d);
+int dcll_conv_lif_backward_any(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                               const float *g_p, const float *g_o, const float *g_pv, const float *g_v, const float *i2o_W,
+                               float *dW, float *db, float *d_outW, float *d_outb, float *scratch, int64_t scratch_floats,
+                               int32_t B, void *stream);
+int dcll_conv_lif_backward_any_open(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                                    const float *g_p, const float *g_o, const float *g_pv, const float *g_v, const float *i2o_W,
+                                    float *d_outW, float *d_outb, float *scratch, int64_t scratch_floats, int32_t B,
+                                    const float **part, int32_t *nchunk, void *stream);
 
 #ifdef __cplusplus
 }

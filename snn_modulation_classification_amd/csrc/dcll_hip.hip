@@ -30,7 +30,8 @@
 //                      drop-in for `.forward`; same pinned order.
 //   (dense twins: k_dense_lif_mfma / k_dense_lif_seq in dcll_dense.hip.)
 //   k_bwd_dv[_nopool], k_bwd_wgrad_c32 (MFMA, 16x16 plane or 16x16 tiles with halo), k_bwd_wgrad (any geometry, row
-//                      bands), k_bwd_reduce[4], k_bwd_outgrad[_part/_reduce]   backward of one layer step (local learning).
+//                      bands), k_bwd_wgrad_any (dcll_bwd_any.hip: MFMA, any plain conv layer, opt-in), k_bwd_reduce[4],
+//                      k_bwd_outgrad[_part/_reduce]   backward of one layer step (local learning).
 //   k_readout_v4 / k_readout_ks / k_readout_rows / k_readout (+ k_readout_sum)   fp32-MFMA GEMMs for i2o / output_:
 //                      many rows, long rows (also split over K with caller scratch), few rows, any shape.
 //   k_argmax, k_vote   per-step argmax and vote.
@@ -3460,8 +3461,10 @@ static int conv_lif_backward_impl(const dcll_conv_desc *d, const float *eps1, co
                                   const float *g_p, const float *g_o, const float *g_pv, const float *g_v,
                                   const float *i2o_W, float *dW, float *db, float *d_outW, float *d_outb,
                                   float *scratch, int64_t scratch_floats, int32_t B, void *stream,
-                                  const float **open_part, int32_t *open_nchunk, bool dv_done = false)
+                                  const float **open_part, int32_t *open_nchunk, bool dv_done = false, bool any = false)
 {
+    // any: the weight gradient by k_bwd_wgrad_any (dcll_bwd_any.hip) whatever the geometry — none of the specialised
+    // kernels, and neither the tap nor the row-width limit of the generic k_bwd_wgrad
     int rc = check_desc(d);
     if (rc) return rc;
     const bool nopool = d->pool_h == 1 && d->pool_w == 1 && d->target <= 32;
@@ -3470,12 +3473,17 @@ static int conv_lif_backward_impl(const dcll_conv_desc *d, const float *eps1, co
         return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward: v may be NULL only for a layer without pooling whose pv is given");
     if (g_p && !i2o_W) return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward: g_p needs i2o_W");
     if (g_o && (!pv_pooled || !d_outW || !d_outb)) return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward: g_o needs pv_pooled, d_outW, d_outb");
-    if (d->kh * d->kw > WG_MAXTAPS) return fail(DCLL_ERR_UNSUPPORTED, "dcll_conv_lif_backward: kernels up to 64 taps (kh * kw <= 64)");
+    if (!any && d->kh * d->kw > WG_MAXTAPS) return fail(DCLL_ERR_UNSUPPORTED, "dcll_conv_lif_backward: kernels up to 64 taps (kh * kw <= 64)");
     if (B < 1) return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward: empty batch");
     hipStream_t st = (hipStream_t)stream;
     int ch, cw, ph, pw;
     conv_shape(d, &ch, &cw, &ph, &pw);
     const long nconv = (long)B * d->c_out * ch * cw;
+    if (any) {      // refusals of this path come before its first launch
+        if ((rc = dcll_bwd_wgrad_any_check(d, "dcll_conv_lif_backward_any")) != DCLL_OK) return rc;
+        if (scratch_floats < nconv + (long)d->c_out * ((long)d->c_in * d->kh * d->kw + 1))
+            return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward_any: scratch too small (need B*c_out*ch*cw + k*(c_out*(c_in*kh*kw+1)), k >= 1)");
+    }
     const char *dv_form = "k_bwd_dv";        // (the generic kernel: pooling, or more than 32 readout rows)
     if (dv_done) {
         // (dcll_conv_lif_backward_open_multi ran this layer's dv with the other layers': the gradient map is in scratch)
@@ -3508,7 +3516,9 @@ static int conv_lif_backward_impl(const dcll_conv_desc *d, const float *eps1, co
     long nchunk = (scratch_floats - nconv) / per_chunk;
     if (nchunk < 1) return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward: scratch too small (need B*c_out*ch*cw + k*(c_out*((c_in/groups)*kh*kw+1)), k >= 1)");
     const bool c32 = d->c_in == 32 && d->c_out == 32 && d->kh == 7 && d->kw == 7 && d->pad_h == 3 && d->pad_w == 3 && plain_conv(d);
-    if (c32 && d->h == 16 && d->w == 16) {
+    if (any) {
+        if ((rc = dcll_launch_bwd_wgrad_any(d, scratch, eps1, part, B, &nchunk, st)) != DCLL_OK) return rc;
+    } else if (c32 && d->h == 16 && d->w == 16) {
         if (nchunk > 256) nchunk = 256;
         if (nchunk > B) nchunk = B;
         // round 6: up to WG32_SPLIT2_MAX_BATCH samples 128 batch chunks x 2 column halves instead of 256 x 1 — half the partial
@@ -3626,6 +3636,27 @@ extern "C" int dcll_conv_lif_backward_open(const dcll_conv_desc *d, const float 
     if (!part || !nchunk) return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward_open: null part / nchunk");
     return conv_lif_backward_impl(d, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, nullptr, nullptr, d_outW, d_outb, scratch,
                                   scratch_floats, B, stream, part, nchunk);
+}
+
+// ABI 9: the same two calls with the weight gradient on k_bwd_wgrad_any (any plain conv layer with c_out <= 32 and a
+// kernel up to 16x16; dcll_conv_lif_backward_any_lds is the predicate)
+extern "C" int dcll_conv_lif_backward_any(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                                          const float *g_p, const float *g_o, const float *g_pv, const float *g_v,
+                                          const float *i2o_W, float *dW, float *db, float *d_outW, float *d_outb,
+                                          float *scratch, int64_t scratch_floats, int32_t B, void *stream)
+{
+    return conv_lif_backward_impl(d, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, dW, db, d_outW, d_outb, scratch,
+                                  scratch_floats, B, stream, nullptr, nullptr, false, true);
+}
+
+extern "C" int dcll_conv_lif_backward_any_open(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                                               const float *g_p, const float *g_o, const float *g_pv, const float *g_v,
+                                               const float *i2o_W, float *d_outW, float *d_outb, float *scratch,
+                                               int64_t scratch_floats, int32_t B, const float **part, int32_t *nchunk, void *stream)
+{
+    if (!part || !nchunk) return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward_any_open: null part / nchunk");
+    return conv_lif_backward_impl(d, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, nullptr, nullptr, d_outW, d_outb, scratch,
+                                  scratch_floats, B, stream, part, nchunk, false, true);
 }
 
 // dcll_conv_lif_backward_open for n layers — the slices of one learning timestep — with their dv launches as ONE launch

@@ -149,6 +149,13 @@ int dcll_launch_seq_w3(const dcll_conv_desc *d, const uint32_t *spk_in, const in
                        const float *tau4, float *eps0, float *eps1, float *arp, uint32_t *spk_out, float *pv_out,
                        float *v_out, bool presigmoid, int32_t T, int32_t B, hipStream_t st);
 
+// k_bwd_wgrad_any (dcll_bwd_any.hip): MFMA weight gradient of any plain conv layer (c_out <= 32, kernel up to 16x16).
+// _check: DCLL_OK or the refusal with its message; the launcher caps *nchunk (partial rows there is room for) and returns it
+__attribute__((visibility("hidden"))) int dcll_bwd_wgrad_any_check(const dcll_conv_desc *d, const char *who);
+__attribute__((visibility("hidden")))
+int dcll_launch_bwd_wgrad_any(const dcll_conv_desc *d, const float *gvf, const float *eps1, float *part, int32_t B,
+                              long *nchunk, hipStream_t st);
+
 // dense twins (dcll_dense.hip): one step as an fp32-MFMA GEMM on the updated traces; all T steps with the state on chip
 __attribute__((visibility("hidden")))
 int dcll_launch_dense_mfma(const dcll_dense_desc *d, const float *eps1, const float *W, const float *b, float *arp,
@@ -239,6 +246,14 @@ __device__ __forceinline__ void static_for(F &&f)
         static_for<R0 + 1, R1>(f);
     }
 }
+
+// (k_lif_seq_any, k_bwd_wgrad_any: geometry at run time) n / d for 0 <= n, d < 65536 as one multiply: M = ceil(2^32 / d) is exact while n * d < 2^32
+struct any_div {
+    uint32_t M;
+    int d;
+};
+static inline any_div make_div(int d) { return any_div{d > 1 ? (uint32_t)(((1ull << 32) + d - 1) / d) : 0u, d}; }
+__device__ __forceinline__ int fdiv(int n, const any_div &q) { return q.d == 1 ? n : (int)__umulhi((uint32_t)n, q.M); }
 
 // A 32-bit LDS address the compiler cannot fold into static offsets (after `asm volatile("" : "+v"(p))`): reads through it are
 // base + immediate, where a visible static offset beyond the instruction's range makes the compiler rebuild a base per read.

@@ -39,14 +39,6 @@ constexpr long ANY_LDS_MAX = 160 * 1024;
 constexpr int ANY_MAX_K = 16, ANY_MAX_COUT = 32;
 constexpr int ANY_KE = 36, ANY_QMAX = 3;        // register form: eps0 values per thread, pixel tiles per wave
 
-// n / d for 0 <= n, d < 65536 as one multiply: M = ceil(2^32 / d) is exact while n * d < 2^32
-struct any_div {
-    uint32_t M;
-    int d;
-};
-static inline any_div make_div(int d) { return any_div{d > 1 ? (uint32_t)(((1ull << 32) + d - 1) / d) : 0u, d}; }
-__device__ __forceinline__ int fdiv(int n, const any_div &q) { return q.d == 1 ? n : (int)__umulhi((uint32_t)n, q.M); }
-
 struct any_geom {
     int c_in, c_out, h, w, kh, kw, pad_h, pad_w, pool_h, pool_w;
     int WP, CHS;                // padded row length, padded channel stride of img

@@ -1131,6 +1131,18 @@ class DCLLBase(nn.Module):
             ops.dense_lif_backward(i2h.make_desc(L.i2o), i2h.state.eps1, pv, res[0], None, None, L.i2o.weight, out=gb)
         return s, p, pv, v, res[2], True
 
+    # -- the MFMA weight gradient of any plain conv layer (k_bwd_wgrad_any, ABI 9): opt-in, beside the default dispatch ------
+    any_learning_path = False       # _learn_tail: dcll_conv_lif_backward_any[_open] instead of dcll_conv_lif_backward[_open]
+
+    def backward_any_supported(self):
+        """True if this slice's native learning step can take its weight gradient from k_bwd_wgrad_any: a Conv2dDCLLlayer built
+        inside the fused step (not _general()) that the library's predicate serves (plain conv, c_out <= 32, kernel up to 16x16,
+        the smallest working set within a workgroup's LDS — ops.backward_any_supported)."""
+        L = self.dclllayer
+        if not isinstance(L, Conv2dDCLLlayer) or L.i2h._general():
+            return False
+        return ops.backward_any_supported(L.i2h.make_desc(L.im_dims, L.pooling, L.i2o.weight.shape[0], L.output_layer))
+
     def _backward_from_pv(self):
         """True if this slice's backward can take sigmoid' from pv: no pooling, <= 32 readout rows (k_bwd_dv_nopool)."""
         L = self.dclllayer
@@ -1141,7 +1153,8 @@ class DCLLBase(nn.Module):
         local-loss gradients (from the readouts' finishing launch where it served them, else dcll_local_loss_grad) and
         dcll_conv_lif_backward into the parameters' .grad.  `open_reduce`: the weight gradient's last reduction is left to
         the caller's ops.grad_reduce_adam (self._learn_bufs['grads']['parts']); `defer_backward` (a list, with open_reduce): the
-        backward is not launched here but appended for ops.conv_lif_backward_open_multi (all slices' dv in one launch).
+        backward is not launched here but appended for ops.conv_lif_backward_open_multi (all slices' dv in one launch) — with
+        any_learning_path the slice's own open call is launched at once instead.
         -> loss (1,) device tensor or None"""
         L = self.dclllayer
         i2h = L.i2h
@@ -1174,7 +1187,7 @@ class DCLLBase(nn.Module):
                 gb.update(d_outW=prm[2].grad, d_outb=prm[3].grad)
             ops.conv_lif_backward(desc, i2h.state.eps1, v, pv, g_p, g_o, None, None, L.i2o.weight,
                                   want_out=L.output_layer, out=gb, open_reduce=open_reduce,
-                                  defer=defer_backward if open_reduce else None)
+                                  defer=defer_backward if open_reduce else None, any_path=self.any_learning_path)
         return loss
 
     def _grads_into_slab(self):

@@ -305,6 +305,7 @@ class ConvNetwork(torch.nn.Module):
             sig += [t.data_ptr() for t in (L.i2h.alpha, L.i2h.tau_m__dt, L.i2h.alphas, L.i2h.tau_s__dt, L.i2o.weight,
                                            L.i2o.bias)]
             walk(s.__dict__.get('_learn_bufs', {}))
+            sig.append(bool(s.any_learning_path))
             for t in s._adam_tensors(advance=False):
                 sig += [t['param'].data_ptr(), t['grad'].data_ptr(), t['exp_avg'].data_ptr(),
                         t['exp_avg_sq'].data_ptr(), t['weight_decay'], t['beta1'], t['beta2'], t['eps']]
@@ -842,6 +843,27 @@ class ConvNetwork(torch.nn.Module):
         if batch_slice is not None and 'o' in res:
             res['o'] = res['o'].clone()
         return res
+
+    # -- the MFMA weight gradient of any plain conv layer (k_bwd_wgrad_any, ABI 9): opt-in, beside the default dispatch ------
+    def backward_any_supported(self):
+        """True if every slice is served by dcll_conv_lif_backward_any (DCLLBase.backward_any_supported)."""
+        return all(s.backward_any_supported() for s in self.dcll_slices)
+
+    @property
+    def any_learning_path(self):
+        """True: every slice's learning step takes its weight gradient from k_bwd_wgrad_any (fp32 MFMA, any plain conv layer with
+        c_out <= 32 and a kernel up to 16x16 — also layers above 64 taps, which the default path refuses) instead of the
+        default dispatch.  The step's structure is unchanged: layer kernels, tails, one dcll_grad_reduce_adam.  Default False;
+        setting it on a network that is not fully served raises DCLLUnsupported."""
+        return all(s.any_learning_path for s in self.dcll_slices)
+
+    @any_learning_path.setter
+    def any_learning_path(self, on):
+        on = bool(on)
+        if on and not self.backward_any_supported():
+            raise ops._lib.DCLLUnsupported('dcll_conv_lif_backward_any does not serve every layer of this network')
+        for s in self.dcll_slices:
+            s.any_learning_path = on            # (part of _graph_signature: a captured timestep of the other path is retaken)
 
     # -- the fused path of any plain conv network (k_lif_seq_any, ABI 8): opt-in, beside test_sequence ---------------------
     def sequence_any_supported(self):

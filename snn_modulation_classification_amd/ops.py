@@ -205,12 +205,30 @@ def conv_lif_step(desc, x, W, b, alpha, tau_m, alphas, tau_s, eps0, eps1, arp, i
     return s, p, o, pv, v
 
 
-def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want_out, out=None, open_reduce=False, defer=None):
+def backward_any_lds(desc):
+    """LDS bytes per workgroup of k_bwd_wgrad_any on this layer, 0 = the layer is not served (dcll_conv_lif_backward_any_lds)."""
+    return int(_lib.get().dcll_conv_lif_backward_any_lds(ctypes.byref(desc)))
+
+
+def backward_any_supported(desc):
+    """True if conv_lif_backward(any_path=True) serves the layer: a plain conv with c_out <= 32, a kernel up to 16x16 and a
+    smallest working set (one column tile's padded eps1 channels + the sample's dv plane) within the 160 KiB of LDS."""
+    return backward_any_lds(desc) > 0
+
+
+BWD_ANY_MAX_CHUNKS = 256        # batch chunks (partial rows) of k_bwd_wgrad_any, at most
+
+
+def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want_out, out=None, open_reduce=False, defer=None,
+                      any_path=False):
     """Gradients of one layer step (dcll_conv_lif_backward) -> (dW, db, d_outW, d_outb).  `out`: optional dict with
     preallocated 'dW', 'db', 'd_outW', 'd_outb', 'bwd_scratch' (the learning loop writes into the parameters' .grad).
     `open_reduce`: dcll_conv_lif_backward_open — dW / db are NOT written yet; the partial rows of the weight gradient stay
     in out['bwd_scratch'] and out['parts'] describes them for grad_reduce_adam, which finishes several layers in one launch.
-    `defer` (a list; open form): nothing is launched — the prepared call is appended for conv_lif_backward_open_multi."""
+    `defer` (a list; open form): nothing is launched — the prepared call is appended for conv_lif_backward_open_multi.
+    `any_path`: dcll_conv_lif_backward_any[_open] — the weight gradient on k_bwd_wgrad_any (fp32 MFMA, any plain conv layer with
+    c_out <= 32 and a kernel up to 16x16; backward_any_supported).  With `defer` the single open call is launched at once (there
+    is no multi-layer form of it) and nothing is appended."""
     B = eps1.shape[0]
     dev = eps1.device
     out = {} if out is None else out
@@ -234,6 +252,8 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
     jobs = B * max(1, (desc.h // 16) * (desc.w // 16))
     per_chunk = desc.c_out * ((desc.c_in // desc.groups) * desc.kh * desc.kw + 1)
     nchunk = min(jobs, 1024 if desc.c_in == 1 else 256)      # (first layer: 128-thread workgroups, 6 KB partial rows)
+    if any_path:
+        nchunk = min(B, BWD_ANY_MAX_CHUNKS)
     part = nchunk * per_chunk
     if want_out and desc.target <= 32 and K % 32 != 0:
         # the output_ gradient's batch chunks (k_bwd_outgrad_part; K % 32 == 0 runs the MFMA form without them): BEHIND the
@@ -248,27 +268,28 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
     # allocator as soon as ptr() returns, and the NEXT temporary's copy can be given the same block (two expanded stride-0
     # gradients in one call would then alias)
     gp_, go_, gpv_, gv_ = c(g_p), (c(g_o) if want_out else None), c(g_pv), c(g_v)
-    if defer is not None:       # (open form, launched later with other layers': conv_lif_backward_open_multi)
+    fn = "dcll_conv_lif_backward_any" if any_path else "dcll_conv_lif_backward"
+    if defer is not None and not any_path:       # (open form, launched later with other layers': conv_lif_backward_open_multi)
         item = _lib.BwdItem(ctypes.pointer(desc), ptr(eps1), ptr(v), ptr(pv_pooled), ptr(gp_), ptr(go_), ptr(gpv_), ptr(gv_),
                             ptr(i2o_W), ptr(d_outW), ptr(d_outb), ptr(scratch), n_scratch, B, 0, None, 0, 0)
         defer.append(dict(item=item, out=out, desc=desc, dW=dW, db=db, scratch=scratch,
                           keep=(eps1, v, pv_pooled, gp_, go_, gpv_, gv_, i2o_W, d_outW, d_outb)))
         return dW, db, d_outW, d_outb
-    if open_reduce:
+    if open_reduce or defer is not None:
         part, nchunk = ctypes.c_void_p(), ctypes.c_int32()
-        rc = _lib.get().dcll_conv_lif_backward_open(
+        rc = getattr(_lib.get(), fn + "_open")(
             ctypes.byref(desc), ptr(eps1), ptr(v), ptr(pv_pooled), ptr(gp_), ptr(go_),
             ptr(gpv_), ptr(gv_), ptr(i2o_W), ptr(d_outW), ptr(d_outb), ptr(scratch), n_scratch, B,
             ctypes.byref(part), ctypes.byref(nchunk), stream_ptr())
-        check(rc, "dcll_conv_lif_backward_open")
+        check(rc, fn + "_open")
         out['parts'] = dict(part=part.value, nchunk=nchunk.value, c_out=desc.c_out,
                             rowlen=(desc.c_in // desc.groups) * desc.kh * desc.kw + 1, dW=dW, db=db, keep=scratch)
         return dW, db, d_outW, d_outb
-    rc = _lib.get().dcll_conv_lif_backward(
+    rc = getattr(_lib.get(), fn)(
         ctypes.byref(desc), ptr(eps1), ptr(v), ptr(pv_pooled), ptr(gp_), ptr(go_),
         ptr(gpv_), ptr(gv_), ptr(i2o_W), ptr(dW), ptr(db), ptr(d_outW), ptr(d_outb), ptr(scratch), n_scratch, B,
         stream_ptr())
-    check(rc, "dcll_conv_lif_backward")
+    check(rc, fn)
     return dW, db, d_outW, d_outb
 
 

@@ -78,6 +78,11 @@ def parse_args(argv=None):
                    help='opt in: the test phase of a network without a geometry-specialised sequence kernel '
                         '(sequence_supported() False, e.g. --data MNIST with mnist_conv.yaml, or RadioML on a 24x24 plane) runs '
                         'ConvNetwork.test_sequence_any (k_lif_seq_any) where it serves every layer, instead of net.test per timestep')
+    p.add_argument('--any_learning_path', action='store_true',
+                   help='opt in: every layer\'s weight gradient of the learning step runs on k_bwd_wgrad_any (fp32 MFMA; any '
+                        'plain conv layer with c_out <= 32 and a kernel up to 16x16, which lifts the default path\'s 64-tap '
+                        'limit) where ConvNetwork.backward_any_supported() holds; ignored with a notice elsewhere.  Whether it '
+                        'is faster than the default dispatch is not measured yet (DESIGN 4.2a; experiments/bwd_any_timing.py)')
     p.add_argument('--gpus', type=int, default=1, metavar='N',
                    help='ranks (one process per GPU): every batch is sharded over them, the local-learning gradients are '
                         'averaged over the ranks every timestep (one bucketed all-reduce)')
@@ -135,6 +140,7 @@ def main(argv=None):
         print('-' * 80)
     net = net.to(pytorch_libdcll.device)
     net.reset(True)
+    _opt_in_any_learning(net, args)
     parallel.freeze_startup_heap()          # (a full GC pass over the start-up heap costs ~100 ms inside the T-loop)
 
     if not args.no_save:
@@ -280,6 +286,16 @@ def main(argv=None):
     return out_dir
 
 
+def _opt_in_any_learning(net, args):
+    """--any_learning_path: switch the network's learning step to k_bwd_wgrad_any where every slice is served."""
+    if not args.any_learning_path:
+        return
+    if net.backward_any_supported():
+        net.any_learning_path = True
+    else:
+        print('--any_learning_path ignored: k_bwd_wgrad_any does not serve every layer of this network')
+
+
 def main_mnist(args):
     """--data MNIST (reference train.py:118-131): 28x28 images as frozen Poisson spike trains (image2spiketrain,
     gain 100), 10 classes, any conv spec that fits 28x28 (networks/mnist_conv.yaml), per-step protocol for learning
@@ -303,6 +319,7 @@ def main_mnist(args):
         print('Loaded the SNN model from `%s`.' % args.restore_path)
     net = net.to(pytorch_libdcll.device)
     net.reset(True)
+    _opt_in_any_learning(net, args)
     parallel.freeze_startup_heap()          # (a full GC pass over the start-up heap costs ~100 ms inside the T-loop)
     n_test = int(np.ceil(float(args.n_test_samples) / args.batch_size_test))
     if args.synthetic:
