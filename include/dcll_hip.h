@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DCLL_ABI_VERSION 9
+#define DCLL_ABI_VERSION 10
 
 enum {
     DCLL_OK = 0,
@@ -563,6 +563,46 @@ int dcll_conv_lif_backward_any_open(const dcll_conv_desc *d, const float *eps1, 
                                     const float *g_p, const float *g_o, const float *g_pv, const float *g_v, const float *i2o_W,
                                     float *d_outW, float *d_outb, float *scratch, int64_t scratch_floats, int32_t B,
                                     const float **part, int32_t *nchunk, void *stream);
+
+/*
+ * ABI 10 — one layer step of ANY plain conv layer in one MFMA launch (k_lif_step_any): dcll_conv_lif_step with the same arguments
+ * and results for the layers that call serves with k_trace + k_conv_lif[_tiled] + k_pool.  Additions only: dcll_conv_lif_step, its
+ * dispatch, launch logs and refusals are unchanged.  Differences to dcll_conv_lif_step:
+ *   scratch    gone: the pooling happens on chip
+ *   w_scratch  new: dcll_conv_lif_step_any_scratch(d) floats — 64 per MFMA step of a chain, 64 (c_in / 2) kh kw + 64 (c_in odd ?
+ *              (kh kw + 1) / 2 : 0); dcll_conv_lif_sequence_any_scratch(d) gives the same wherever THAT call serves the layer —: the weights in MFMA fragment order, written by k_seq_any_wprep in front of
+ *              the layer kernel on EVERY call — there is no "already prepared" form, the learning step changes W behind it
+ *   opts       none: fp32 weights only
+ * As there: dense fp32 x of any values; b may be NULL; scalar or (c_in,h,w) time constants (tau_is_tensor); eps0 / eps1 / arp
+ * updated in place; out_v may be NULL; p / o only when i2o_W && out_p / output_layer, through the same readout kernels;
+ * B == 0: DCLL_OK, nothing is looked at.  Pointers need 4-byte alignment only.
+ * Served (else DCLL_ERR_UNSUPPORTED, before any launch): stride = dilation = groups = 1; any c_in; c_out <= 32; kh, kw <= 16; any
+ * padding, pooling and batch; and a working set within the 160 KiB of LDS of a workgroup:
+ *   4 bytes x (c_in (h + 2 pad_h)(w + 2 pad_w) [zero-padded eps1 image] + (pooling != 1 ? c_out ch cw : 0) [v plane of the
+ *   pooling pass] + 32 [bias]).
+ * dcll_conv_lif_step_any_lds returns these bytes, dcll_conv_lif_step_any_scratch the floats of w_scratch; both 0 for a descriptor
+ * that is not served (invalid ones included).
+ * DCLL_ERR_INVALID, before any launch: a NULL required pointer (w_scratch included), a refractory layer without arp, an output
+ * layer without out_W / out_o, B < 0.
+ * Arithmetic: the contract at the top of this file and the rule of dcll_conv_lif_sequence_any — the traces are three separately
+ * rounded operations each; every v is ONE fmaf chain from b[co] over (cp, ky, kx, h) on v_mfma_f32_32x32x2_f32, two consecutive
+ * links per instruction; the unpaired last channel of an odd c_in runs its taps two by two; a chain of odd length ends with
+ * fmaf(0, 0, acc).  v equals dcll_conv_lif_step bit for bit up to the sign of a zero; spikes, eps0, eps1 and arp bit for bit; pv
+ * within the sigmoid's 1e-4.  Pooled outputs: max over the window of v, spike = pooled v > 0, pv = sigmoid(pooled v).
+ * Forms (the launch log names them; R = refractory; k_seq_any_wprep in front of each):
+ *   "k_lif_step_any<R>"                      one workgroup per sample: traces, chains and epilogue in one launch
+ *   "k_lif_step_any<R> (pooling)"            the same with the v plane and the pooling pass in LDS
+ *   "k_trace", "k_lif_step_any<R> (split)"   NS > 1 workgroups per sample for a layer without pooling, NS = min(ceil(tiles / 8),
+ *                                            256 / B) reduced to the fewest workgroups with as many tiles each (tiles = ceil(ch cw
+ *                                            / 32)); the traces advance in k_trace BEFORE the layer kernel, because workgroups of
+ *                                            one sample read each other's halo rows.  Results do not depend on NS.
+ */
+int64_t dcll_conv_lif_step_any_lds(const dcll_conv_desc *d);
+int64_t dcll_conv_lif_step_any_scratch(const dcll_conv_desc *d);
+int dcll_conv_lif_step_any(const dcll_conv_desc *d, const float *x, const float *W, const float *b, const float *alpha,
+                           const float *tau_m, const float *alphas, const float *tau_s, float *eps0, float *eps1, float *arp,
+                           const float *i2o_W, const float *i2o_b, const float *out_W, const float *out_b, float *out_s,
+                           float *out_p, float *out_o, float *out_pv, float *out_v, float *w_scratch, int32_t B, void *stream);
 
 #ifdef __cplusplus
 }

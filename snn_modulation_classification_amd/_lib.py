@@ -13,7 +13,7 @@ SO_PATH = os.environ.get("DCLL_HIP_SO") or os.path.join(_PKG, "libdcll_hip.so")
 CSRC = os.path.join(_PKG, "csrc")
 
 DCLL_OK, DCLL_ERR_INVALID, DCLL_ERR_UNSUPPORTED, DCLL_ERR_LAUNCH = 0, -1, -2, -3
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 
 class DCLLHipError(RuntimeError):
@@ -149,6 +149,9 @@ SIGNATURES = {
     "dcll_conv_lif_backward_any_lds": (_I64, [_DP]),
     "dcll_conv_lif_backward_any": (_I32, [_DP] + [_P] * 13 + [_I64, _I32, _P]),
     "dcll_conv_lif_backward_any_open": (_I32, [_DP] + [_P] * 11 + [_I64, _I32, ctypes.POINTER(ctypes.c_void_p), _IP, _P]),
+    "dcll_conv_lif_step_any_lds": (_I64, [_DP]),
+    "dcll_conv_lif_step_any_scratch": (_I64, [_DP]),
+    "dcll_conv_lif_step_any": (_I32, [_DP] + [_P] * 20 + [_I32, _P]),
 }
 
 

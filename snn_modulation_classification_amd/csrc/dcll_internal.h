@@ -156,6 +156,21 @@ __attribute__((visibility("hidden")))
 int dcll_launch_bwd_wgrad_any(const dcll_conv_desc *d, const float *gvf, const float *eps1, float *part, int32_t B,
                               long *nchunk, hipStream_t st);
 
+// k_seq_any_wprep (dcll_seq_any.hip): the weights of a plain conv layer in MFMA fragment order, 64 floats per chain step
+// (_steps: (c_in / 2) kh kw + (c_in odd: (kh kw + 1) / 2)) — shared by k_lif_seq_any and k_lif_step_any
+__attribute__((visibility("hidden"))) long dcll_seq_any_steps(const dcll_conv_desc *d);
+__attribute__((visibility("hidden"))) int dcll_launch_seq_any_wprep(const dcll_conv_desc *d, const float *W, float *wperm, hipStream_t st);
+
+// k_lif_step_any (dcll_step_any.hip): one MFMA layer step of any plain conv layer (c_out <= 32, kernel up to 16x16).
+// _check: DCLL_OK or the refusal with its message; _split: workgroups per sample (> 1: the caller runs k_trace first);
+// the launcher with launch == false only prepares (checks, LDS reservation): called before the first launch of the entry point
+__attribute__((visibility("hidden"))) int dcll_step_any_check(const dcll_conv_desc *d, const char *who);
+__attribute__((visibility("hidden"))) int dcll_step_any_split(const dcll_conv_desc *d, int32_t B);
+__attribute__((visibility("hidden")))
+int dcll_launch_step_any(const dcll_conv_desc *d, const float *x, const float *wperm, const float *b, const float *alpha,
+                         const float *tau_m, const float *alphas, const float *tau_s, float *eps0, float *eps1, float *arp,
+                         float *out_s, float *out_pv, float *out_v, int ns, int32_t B, hipStream_t st, bool launch);
+
 // dense twins (dcll_dense.hip): one step as an fp32-MFMA GEMM on the updated traces; all T steps with the state on chip
 __attribute__((visibility("hidden")))
 int dcll_launch_dense_mfma(const dcll_dense_desc *d, const float *eps1, const float *W, const float *b, float *arp,
@@ -247,7 +262,7 @@ __device__ __forceinline__ void static_for(F &&f)
     }
 }
 
-// (k_lif_seq_any, k_bwd_wgrad_any: geometry at run time) n / d for 0 <= n, d < 65536 as one multiply: M = ceil(2^32 / d) is exact while n * d < 2^32
+// (k_lif_seq_any, k_bwd_wgrad_any, k_lif_step_any: geometry at run time) n / d for 0 <= n, d < 65536 as one multiply: M = ceil(2^32 / d) is exact while n * d < 2^32
 struct any_div {
     uint32_t M;
     int d;

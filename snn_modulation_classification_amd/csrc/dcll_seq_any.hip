@@ -124,6 +124,16 @@ __global__ void k_seq_any_wprep(const float *__restrict__ W, float *__restrict__
     wperm[i] = (co < c_out && tap < KK) ? W[((long)co * c_in + ci) * KK + tap] : 0.0f;
 }
 
+long dcll_seq_any_steps(const dcll_conv_desc *d) { return any_steps(d); }
+int dcll_launch_seq_any_wprep(const dcll_conv_desc *d, const float *W, float *wperm, hipStream_t st)
+{
+    const int npair = (d->c_in / 2) * d->kh * d->kw, nsteps = (int)any_steps(d);
+    hipLaunchKernelGGL(k_seq_any_wprep, dim3((nsteps * 64 + 255) / 256), dim3(256), 0, st, W, wperm, d->c_in, d->c_out, d->kh, d->kw,
+                       npair, nsteps);
+    HIP_CHECK_LAUNCH("k_seq_any_wprep");
+    return DCLL_OK;
+}
+
 template <bool R, bool WLDS, bool REGS>
 __global__ __launch_bounds__(ANY_THREADS) void k_lif_seq_any(const any_geom g, const uint32_t *__restrict__ spk_in,
                                                             const float *__restrict__ wperm, const float *__restrict__ bias,
@@ -447,9 +457,7 @@ extern "C" int dcll_conv_lif_sequence_any(const dcll_conv_desc *d, const uint32_
     const bool wlds = !regs && g.nwl == g.nsteps;
     const size_t lds_bytes = (size_t)(base + (long)g.nwl * 64) * 4;
 
-    hipLaunchKernelGGL(k_seq_any_wprep, dim3((g.nsteps * 64 + 255) / 256), dim3(256), 0, st, W, w_scratch, g.c_in, g.c_out, g.kh,
-                       g.kw, g.npair, g.nsteps);
-    HIP_CHECK_LAUNCH("k_seq_any_wprep");
+    if ((rc = dcll_launch_seq_any_wprep(d, W, w_scratch, st)) != DCLL_OK) return rc;
     // launch-log names: k_lif_seq_any<refractory, weights in LDS, register form>
 #define DCLL_ANY(R_, L_, G_)                                                                                                  \
     return launch_any<R_, L_, G_>(g, lds_bytes, spk_in, w_scratch, b, tau4, eps0, eps1, arp, spk_out, pv_out, v_out, T, B,    \

@@ -282,10 +282,16 @@ class ContinuousConv2D(nn.Module):
                 rows.append(flat[:, 0])
         return torch.stack(rows).contiguous()
 
+    # _step: dcll_conv_lif_step_any (k_lif_step_any, ABI 10) instead of dcll_conv_lif_step; opt-in.  The supported switch is
+    # ConvNetwork.any_step_path, which asks step_any_supported() first; set here directly, a layer the library refuses (or one
+    # given int8 weights afterwards) raises DCLLUnsupported / ValueError from every step — there is no fall-back
+    any_step_path = False
+
     def _step(self, input, pooling=(1, 1), i2o=None, output_=None, out=None, stacked=None, finish=None, want_v=True,
               defer_ro=False):
-        """Run one step through dcll_conv_lif_step; returns (s_pooled, p, o, pv_pooled, v).  `out`: optional dict of
-        reusable output buffers; `stacked` / `finish` / `defer_ro`: the fused readout tail of the step (ops.conv_lif_step)."""
+        """Run one step through dcll_conv_lif_step (any_step_path: dcll_conv_lif_step_any); returns (s_pooled, p, o, pv_pooled,
+        v).  `out`: optional dict of reusable output buffers; `stacked` / `finish` / `defer_ro`: the fused readout tail of the
+        step (ops.conv_lif_step)."""
         self._check_batch(input)
         desc = self.make_desc(input.shape[2:4], pooling, 0 if i2o is None else i2o.weight.shape[0],
                               output_ is not None)
@@ -297,7 +303,8 @@ class ContinuousConv2D(nn.Module):
                 st.eps0, st.eps1, arp,
                 None if i2o is None else i2o.weight, None if i2o is None else i2o.bias,
                 None if output_ is None else output_.weight, None if output_ is None else output_.bias, out=out,
-                q8=self.int8_weights(), stacked=stacked, finish=finish, want_v=want_v, defer_ro=defer_ro)
+                q8=self.int8_weights(), stacked=stacked, finish=finish, want_v=want_v, defer_ro=defer_ro,
+                any_path=self.any_step_path)
 
     def _general(self):
         """True when the layer was built with an option outside the fused step (see _is_sigmoid)."""
@@ -677,6 +684,16 @@ class Conv2dDCLLlayer(nn.Module):
                                                want_spikes=want_spikes, want_pv=want_pv, out=buffers,
                                                lowhigh_iter0=lowhigh_iter0, q8=q8, presigmoid=presigmoid)
         return spk, pv, None
+
+    # -- the MFMA per-step forward of any plain conv layer (k_lif_step_any, ABI 10): opt-in through i2h.any_step_path --------
+    def step_any_supported(self):
+        """True if dcll_conv_lif_step_any serves this layer's steps: built inside the fused step (not _general()), fp32 weights
+        (no int8 form) and the library's own predicate (plain conv, c_out <= 32, kernel up to 16x16, the padded eps1 image and a
+        pooling layer's v plane within a workgroup's LDS — ops.step_any_supported)."""
+        i = self.i2h
+        if i._general() or i.int8_weights() is not None:
+            return False
+        return ops.step_any_supported(i.make_desc(self.im_dims, self.pooling, self.target_size, self.output_layer))
 
     # -- the fused path of any plain conv layer (k_lif_seq_any, ABI 8): opt-in, beside sequence_kind / forward_sequence ---
     def sequence_any_supported(self):
@@ -1142,6 +1159,11 @@ class DCLLBase(nn.Module):
         if not isinstance(L, Conv2dDCLLlayer) or L.i2h._general():
             return False
         return ops.backward_any_supported(L.i2h.make_desc(L.im_dims, L.pooling, L.i2o.weight.shape[0], L.output_layer))
+
+    def step_any_supported(self):
+        """True if this slice's layer steps can run on k_lif_step_any (Conv2dDCLLlayer.step_any_supported)."""
+        L = self.dclllayer
+        return isinstance(L, Conv2dDCLLlayer) and L.step_any_supported()
 
     def _backward_from_pv(self):
         """True if this slice's backward can take sigmoid' from pv: no pooling, <= 32 readout rows (k_bwd_dv_nopool)."""

@@ -306,6 +306,7 @@ class ConvNetwork(torch.nn.Module):
                                            L.i2o.bias)]
             walk(s.__dict__.get('_learn_bufs', {}))
             sig.append(bool(s.any_learning_path))
+            sig.append(bool(L.i2h.any_step_path))
             for t in s._adam_tensors(advance=False):
                 sig += [t['param'].data_ptr(), t['grad'].data_ptr(), t['exp_avg'].data_ptr(),
                         t['exp_avg_sq'].data_ptr(), t['weight_decay'], t['beta1'], t['beta2'], t['eps']]
@@ -526,6 +527,7 @@ class ConvNetwork(torch.nn.Module):
                 sig += [L.output_.weight.data_ptr(), L.output_.bias.data_ptr()]
             q8 = L.i2h.int8_weights()            # (a capture taken on the int8 form must not outlive it)
             sig.append(None if q8 is None else (q8[0].data_ptr(), q8[1].data_ptr()))
+            sig.append(bool(L.i2h.any_step_path))
         return tuple(sig)
 
     @torch.no_grad()
@@ -574,6 +576,21 @@ class ConvNetwork(torch.nn.Module):
     def reset(self, init_states=False):
         for s in self.dcll_slices:
             s.init(self.batch_size, init_states=init_states)
+        if init_states:
+            self._opt_in_from_environment()
+
+    def _opt_in_from_environment(self):
+        """DCLL_ANY_STEP_PATH=1 in the environment = `net.any_step_path = True` at the network's first reset(True), for the entry
+        points without a flag of their own (test_radio_ml.py: `DCLL_ANY_STEP_PATH=1 python test_radio_ml.py --no_sequence_path`
+        runs its per-step loop on k_lif_step_any).  Ignored with a notice where a layer is not served; unset or 0: nothing
+        changes.  Looked at once per network, so a later `net.any_step_path = False` holds."""
+        if self.__dict__.get('_any_step_env_seen') or os.environ.get('DCLL_ANY_STEP_PATH', '0') in ('', '0'):
+            return
+        self.__dict__['_any_step_env_seen'] = True
+        if self.step_any_supported():
+            self.any_step_path = True
+        else:
+            print('DCLL_ANY_STEP_PATH ignored: k_lif_step_any does not serve every layer of this network')
 
     def write_stats(self, writer, epoch, comment=''):
         for s in self.dcll_slices:
@@ -864,6 +881,28 @@ class ConvNetwork(torch.nn.Module):
             raise ops._lib.DCLLUnsupported('dcll_conv_lif_backward_any does not serve every layer of this network')
         for s in self.dcll_slices:
             s.any_learning_path = on            # (part of _graph_signature: a captured timestep of the other path is retaken)
+
+    # -- the MFMA per-step forward of any plain conv layer (k_lif_step_any, ABI 10): opt-in, beside the default dispatch -------
+    def step_any_supported(self):
+        """True if every layer's steps are served by dcll_conv_lif_step_any (Conv2dDCLLlayer.step_any_supported)."""
+        return all(s.step_any_supported() for s in self.dcll_slices)
+
+    @property
+    def any_step_path(self):
+        """True: every per-step layer call — net.test(x[t]), every learning timestep, Conv2dDCLLlayer.forward, the autograd
+        nodes — runs k_lif_step_any (one fp32-MFMA launch with the traces and the pooling fused in; any plain conv layer with
+        c_out <= 32 and a kernel up to 16x16) instead of dcll_conv_lif_step's dispatch.  The readout tails and the sequence
+        calls (test_sequence, test_sequence_any) are untouched.  Default False; setting it on a network that is not fully
+        served (c_out 64, int8 weights) raises DCLLUnsupported."""
+        return all(s.dclllayer.i2h.any_step_path for s in self.dcll_slices)
+
+    @any_step_path.setter
+    def any_step_path(self, on):
+        on = bool(on)
+        if on and not self.step_any_supported():
+            raise ops._lib.DCLLUnsupported('dcll_conv_lif_step_any does not serve every layer of this network')
+        for s in self.dcll_slices:
+            s.dclllayer.i2h.any_step_path = on  # (part of _graph_signature and _test_signature: a capture of the other path is retaken)
 
     # -- the fused path of any plain conv network (k_lif_seq_any, ABI 8): opt-in, beside test_sequence ---------------------
     def sequence_any_supported(self):

@@ -111,7 +111,8 @@ def _check_layer_operands(desc, W, b, eps0, eps1, arp, B, tau=None, tau4=None):
 
 
 def conv_lif_step(desc, x, W, b, alpha, tau_m, alphas, tau_s, eps0, eps1, arp, i2o_W=None, i2o_b=None,
-                  out_W=None, out_b=None, want_v=True, out=None, q8=None, stacked=None, finish=None, defer_ro=False):
+                  out_W=None, out_b=None, want_v=True, out=None, q8=None, stacked=None, finish=None, defer_ro=False,
+                  any_path=False):
     """One Conv2dDCLLlayer.forward step (dcll/pytorch_libdcll.py:599-608); state tensors are updated in place.
 
     Returns (s_pooled, p, o, pv_pooled, v) — p / o are None when the corresponding weights are None.
@@ -126,7 +127,12 @@ def conv_lif_step(desc, x, W, b, alpha, tau_m, alphas, tau_s, eps0, eps1, arp, i
     `defer_ro` (needs `finish`): where the fused readout tail serves the shape, only the layer kernel is launched now; the
     readout tail is left in finish['run_readouts'] for the caller to launch later (p / o are unwritten until then) — a
     learning timestep launches all layer kernels first (layer l+1 needs layer l's spikes, not its readouts).
+    `any_path`: the layer kernel is dcll_conv_lif_step_any — k_lif_step_any, one fp32-MFMA launch with the traces and the pooling
+    fused in, for any plain conv layer with c_out <= 32 and a kernel up to 16x16 (step_any_supported) — instead of
+    dcll_conv_lif_step's dispatch; the readout tails are the same.  fp32 weights only: with `q8` it raises.
     """
+    if any_path and q8 is not None:
+        raise ValueError("conv_lif_step(any_path=True) reads fp32 weights only (no q8)")
     out = {} if out is None else out
     B = x.shape[0]
     ch, cw, ph, pw = conv_out_shape(desc)
@@ -155,7 +161,18 @@ def conv_lif_step(desc, x, W, b, alpha, tau_m, alphas, tau_s, eps0, eps1, arp, i
     v = buf('v', (B, desc.c_out, ch, cw), want_v)
     p = buf('p', (B, desc.target), i2o_W is not None)
     o = buf('o', (B, desc.target), bool(desc.output_layer))
-    scratch = buf('scratch', (2, B, desc.c_out, ch, cw), pooled)
+    scratch = buf('scratch', (2, B, desc.c_out, ch, cw), pooled and not any_path)
+    w_scratch = buf('w_scratch', (max(step_any_scratch(desc), 1),), True) if any_path else None       # (not served: the call refuses)
+
+    def layer_step(d, *readout_args):
+        """the layer call of this step: dcll_conv_lif_step, or dcll_conv_lif_step_any (w_scratch for scratch, no opts)"""
+        fn = "dcll_conv_lif_step_any" if any_path else "dcll_conv_lif_step"
+        tail = (ptr(w_scratch),) if any_path else (ptr(scratch), opts)
+        rc = getattr(_lib.get(), fn)(
+            ctypes.byref(d), ptr(x), ptr(W), ptr(b), ptr(alpha), ptr(tau_m), ptr(alphas), ptr(tau_s),
+            ptr(eps0), ptr(eps1), ptr(arp), *readout_args, ptr(pv), ptr(v), *tail, B, stream_ptr())
+        check(rc, fn)
+
     if finish is not None:
         finish['done'] = False
     n2 = desc.target if desc.output_layer else 0
@@ -167,11 +184,7 @@ def conv_lif_step(desc, x, W, b, alpha, tau_m, alphas, tau_s, eps0, eps1, arp, i
         # launch (slice sums, p / o, the recorded argmax, the local-loss gradients)
         d2 = ConvDesc.from_buffer_copy(desc)
         d2.output_layer = 0
-        rc = _lib.get().dcll_conv_lif_step(
-            ctypes.byref(d2), ptr(x), ptr(W), ptr(b), ptr(alpha), ptr(tau_m), ptr(alphas), ptr(tau_s),
-            ptr(eps0), ptr(eps1), ptr(arp), None, None, None, None,
-            ptr(s), None, None, ptr(pv), ptr(v), ptr(scratch), opts, B, stream_ptr())
-        check(rc, "dcll_conv_lif_step")
+        layer_step(d2, None, None, None, None, ptr(s), None, None)
         Wt, bias = (i2o_W, i2o_b) if stacked is None else stacked
         if defer_ro and finish is not None:
             finish['run_readouts'] = lambda: step_readouts(pv.reshape(B, -1), Wt, bias, desc.target, n2, p, o, scratch=out,
@@ -188,21 +201,29 @@ def conv_lif_step(desc, x, W, b, alpha, tau_m, alphas, tau_s, eps0, eps1, arp, i
         # rows/4 x N/4 workgroups that re-read every pv row N/4 times
         d2 = ConvDesc.from_buffer_copy(desc)
         d2.output_layer = 0
-        rc = _lib.get().dcll_conv_lif_step(
-            ctypes.byref(d2), ptr(x), ptr(W), ptr(b), ptr(alpha), ptr(tau_m), ptr(alphas), ptr(tau_s),
-            ptr(eps0), ptr(eps1), ptr(arp), None, None, None, None,
-            ptr(s), None, None, ptr(pv), ptr(v), ptr(scratch), opts, B, stream_ptr())
-        check(rc, "dcll_conv_lif_step")
+        layer_step(d2, None, None, None, None, ptr(s), None, None)
         readout(pv.reshape(B, -1), i2o_W, i2o_b, out=p, scratch=out)
         if desc.output_layer:
             readout(pv.reshape(B, -1), out_W, out_b, out=o, scratch=out)
         return s, p, o, pv, v
-    rc = _lib.get().dcll_conv_lif_step(
-        ctypes.byref(desc), ptr(x), ptr(W), ptr(b), ptr(alpha), ptr(tau_m), ptr(alphas), ptr(tau_s),
-        ptr(eps0), ptr(eps1), ptr(arp), ptr(i2o_W), ptr(i2o_b), ptr(out_W), ptr(out_b),
-        ptr(s), ptr(p), ptr(o), ptr(pv), ptr(v), ptr(scratch), opts, B, stream_ptr())
-    check(rc, "dcll_conv_lif_step")
+    layer_step(desc, ptr(i2o_W), ptr(i2o_b), ptr(out_W), ptr(out_b), ptr(s), ptr(p), ptr(o))
     return s, p, o, pv, v
+
+
+def step_any_lds(desc):
+    """LDS bytes per workgroup of k_lif_step_any on this layer, 0 = the layer is not served (dcll_conv_lif_step_any_lds)."""
+    return int(_lib.get().dcll_conv_lif_step_any_lds(ctypes.byref(desc)))
+
+
+def step_any_supported(desc):
+    """True if conv_lif_step(any_path=True) serves the layer: a plain conv with c_out <= 32, a kernel up to 16x16 and a working
+    set (the zero-padded eps1 image, the v plane of a pooling layer) within the 160 KiB of LDS."""
+    return step_any_lds(desc) > 0
+
+
+def step_any_scratch(desc):
+    """Floats of dcll_conv_lif_step_any's w_scratch (dcll_conv_lif_step_any_scratch: 64 per MFMA step of a chain), 0 = not served."""
+    return int(_lib.get().dcll_conv_lif_step_any_scratch(ctypes.byref(desc)))
 
 
 def backward_any_lds(desc):

@@ -83,6 +83,12 @@ def parse_args(argv=None):
                         'plain conv layer with c_out <= 32 and a kernel up to 16x16, which lifts the default path\'s 64-tap '
                         'limit) where ConvNetwork.backward_any_supported() holds; ignored with a notice elsewhere.  Whether it '
                         'is faster than the default dispatch is not measured yet (DESIGN 4.2a; experiments/bwd_any_timing.py)')
+    p.add_argument('--any_step_path', action='store_true',
+                   help='opt in: every per-step layer call (net.test per timestep, every learning timestep) runs k_lif_step_any '
+                        '(one fp32-MFMA launch with the traces and the pooling fused in; any plain conv layer with c_out <= 32 and '
+                        'a kernel up to 16x16) where ConvNetwork.step_any_supported() holds; ignored with a notice elsewhere.  '
+                        'The sequence paths are not affected.  Not yet measured against the default path (DESIGN 4.2b; '
+                        'experiments/step_any_timing.py)')
     p.add_argument('--gpus', type=int, default=1, metavar='N',
                    help='ranks (one process per GPU): every batch is sharded over them, the local-learning gradients are '
                         'averaged over the ranks every timestep (one bucketed all-reduce)')
@@ -141,6 +147,7 @@ def main(argv=None):
     net = net.to(pytorch_libdcll.device)
     net.reset(True)
     _opt_in_any_learning(net, args)
+    _opt_in_any_step(net, args)
     parallel.freeze_startup_heap()          # (a full GC pass over the start-up heap costs ~100 ms inside the T-loop)
 
     if not args.no_save:
@@ -296,6 +303,16 @@ def _opt_in_any_learning(net, args):
         print('--any_learning_path ignored: k_bwd_wgrad_any does not serve every layer of this network')
 
 
+def _opt_in_any_step(net, args):
+    """--any_step_path: switch the network's per-step layer calls to k_lif_step_any where every layer is served."""
+    if not args.any_step_path:
+        return
+    if net.step_any_supported():
+        net.any_step_path = True
+    else:
+        print('--any_step_path ignored: k_lif_step_any does not serve every layer of this network')
+
+
 def main_mnist(args):
     """--data MNIST (reference train.py:118-131): 28x28 images as frozen Poisson spike trains (image2spiketrain,
     gain 100), 10 classes, any conv spec that fits 28x28 (networks/mnist_conv.yaml), per-step protocol for learning
@@ -320,6 +337,7 @@ def main_mnist(args):
     net = net.to(pytorch_libdcll.device)
     net.reset(True)
     _opt_in_any_learning(net, args)
+    _opt_in_any_step(net, args)
     parallel.freeze_startup_heap()          # (a full GC pass over the start-up heap costs ~100 ms inside the T-loop)
     n_test = int(np.ceil(float(args.n_test_samples) / args.batch_size_test))
     if args.synthetic:
