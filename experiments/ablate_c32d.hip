@@ -5,9 +5,10 @@
 //                            does: how much does a stage of the layer kernel stretch?
 //   ./ablate_c32d presig     pv_presigmoid (round 3): the epilogue stores v instead of sigmoid(v) — launch time and the
 //                            stamps of the non-MFMA phase with and without the four sigmoids per wave and stage
-//   ./ablate_c32d tp         the time-paired k_lif_seq_c32d (a tile = one image row at two timesteps, every padded tap row
-//                            skipped) against the row-paired k_lif_seq_c32rp: launch times and stage stamps of both, and
-//                            the time-paired chain phase alone (no trace update, no epilogue)
+//   ./ablate_c32d tp         the time-paired, output-stationary k_lif_seq_c32d (a tile = one image row at two timesteps,
+//                            accumulators stay in their wave, weights streamed from the copy k_c32d_wfrag makes) against the
+//                            row-paired systolic k_lif_seq_c32rp: launch times of both, stage stamps of k_lif_seq_c32rp
+//                            (k_lif_seq_c32d has no stages and carries no stamp variant)
 #include "../snn_modulation_classification_amd/csrc/dcll_hip.hip"
 #include <vector>
 int main(int argc, char **argv)
@@ -47,26 +48,26 @@ int main(int argc, char **argv)
         for (int i = 0; i < n; ++i) dcll_launch_readout_direct(pv2, Wro, nullptr, ro, (long)T * B, 8192, 24, side);
     };
     if (tp) {
-        const char *names[3] = {"k_lif_seq_c32rp (row-paired)", "k_lif_seq_c32d (time-paired)", "k_lif_seq_c32d, chain phase only"};
-        for (int mode = 0; mode < 3; ++mode) {
-            for (int rep = 0; rep < 3 && mode < 2; ++rep) {
+        const char *names[2] = {"k_lif_seq_c32rp (row-paired)", "k_lif_seq_c32d (time-paired, output-stationary)"};
+        float *wfrag;
+        hipMalloc(&wfrag, OS_WFRAG_FLOATS * 4);
+        for (int mode = 0; mode < 2; ++mode) {
+            for (int rep = 0; rep < 3; ++rep) {
                 hipMemset(e0, 0, ns * 4); hipMemset(e1, 0, ns * 4); hipMemset(arp, 0, ns * 4);
                 hipEventRecord(a);
                 if (mode == 0)
                     hipLaunchKernelGGL((k_lif_seq_c32rp<true, 1, 0>), dim3(B), dim3(512), 0, 0, spk_in, dcll_wsrc{W, nullptr, nullptr}, bias, tau4, e0, e1, arp, spk_out, pv, (float *)nullptr, T, B, 0.65f, 1.0f);
-                else
-                    hipLaunchKernelGGL((k_lif_seq_c32d<true, 1, 0>), dim3(B), dim3(512), 0, 0, spk_in, dcll_wsrc{W, nullptr, nullptr}, bias, tau4, e0, e1, arp, spk_out, pv, (float *)nullptr, T, B, 0.65f, 1.0f);
+                else {          // (the helper is part of every product call: timed with the kernel)
+                    hipLaunchKernelGGL(k_c32d_wfrag, dim3(OS_WFRAG_FLOATS / 256), dim3(256), 0, 0, dcll_wsrc{W, nullptr, nullptr}, wfrag);
+                    hipLaunchKernelGGL((k_lif_seq_c32d<true, 1>), dim3(B), dim3(512), 0, 0, spk_in, wfrag, bias, tau4, e0, e1, arp, spk_out, pv, (float *)nullptr, T, B, 0.65f, 1.0f);
+                }
                 hipEventRecord(b); hipEventSynchronize(b);
                 float ms; hipEventElapsedTime(&ms, a, b);
                 printf("%s B=%d T=%d: %.3f ms\n", names[mode], B, T, ms);
             }
+            if (mode == 1) continue;
             hipMemset(dbg, 0, 4096);
-            if (mode == 0)
-                hipLaunchKernelGGL((k_lif_seq_c32rp<true, 1, 1>), dim3(B), dim3(512), 0, 0, spk_in, dcll_wsrc{W, nullptr, nullptr}, bias, tau4, e0, e1, arp, spk_out, pv, (float *)dbg, T, B, 0.65f, 1.0f);
-            else if (mode == 1)
-                hipLaunchKernelGGL((k_lif_seq_c32d<true, 1, 1>), dim3(B), dim3(512), 0, 0, spk_in, dcll_wsrc{W, nullptr, nullptr}, bias, tau4, e0, e1, arp, spk_out, pv, (float *)dbg, T, B, 0.65f, 1.0f);
-            else
-                hipLaunchKernelGGL((k_lif_seq_c32d<true, 1, 9>), dim3(B), dim3(512), 0, 0, spk_in, dcll_wsrc{W, nullptr, nullptr}, bias, tau4, e0, e1, arp, spk_out, pv, (float *)dbg, T, B, 0.65f, 1.0f);
+            hipLaunchKernelGGL((k_lif_seq_c32rp<true, 1, 1>), dim3(B), dim3(512), 0, 0, spk_in, dcll_wsrc{W, nullptr, nullptr}, bias, tau4, e0, e1, arp, spk_out, pv, (float *)dbg, T, B, 0.65f, 1.0f);
             hipDeviceSynchronize();
             unsigned long long h4[64];
             hipMemcpy(h4, dbg, 512, hipMemcpyDeviceToHost);

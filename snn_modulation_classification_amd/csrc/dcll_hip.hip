@@ -12,8 +12,10 @@
 // -ffp-contract=off is part of the arithmetic contract: the trace lines are three separately rounded ops.
 //
 // Kernels
-//   k_lif_seq_c32d     the hot kernel (even T >= 8): k_lif_seq_c32 with two tiles per wave and stage, a tile = one image row at
-//                      two timesteps — see its header.   k_lif_seq_c32rp: its row-paired predecessor, kept for odd T >= 8.
+//   k_lif_seq_c32d     the hot kernel (even T >= 8): output-stationary — a wave keeps two tiles (a tile = one image row at two
+//                      timesteps) from the bias to the epilogue, the weights are streamed from the fragment-ordered copy that
+//                      k_c32d_wfrag makes in front of every launch — see its header.   k_lif_seq_c32rp: the row-paired systolic
+//                      predecessor, kept for odd T >= 8.
 //   k_lif_seq_c32      one 32->32 7x7 layer, ALL T timesteps, one sample per workgroup (short sequences, per-step calls).
 //                      8 waves; wave w owns input channels 4w..4w+3 (a K-slice of the implicit GEMM):
 //                      their eps0/eps1 traces (registers + a zero-padded LDS image) and the 2x49 weight
@@ -38,6 +40,9 @@
 //   k_iq_encode, k_pack, k_unpack, k_permute_readout     glue.
 // The kernels for planes larger than 16x16 (k_lif_seq_c32t, k_lif_seq_c1t) live in dcll_seq_tiled.hip.
 #include "dcll_internal.h"
+#include <map>
+#include <mutex>
+#include <utility>
 
 static thread_local char g_err[DCLL_ERR_LEN] = "";
 char *dcll_err_buf(void) { return g_err; }
@@ -1976,375 +1981,361 @@ __global__ __launch_bounds__(512) void k_lif_seq_c32rp(const uint32_t *__restric
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// k_lif_seq_c32d — THE HOT KERNEL (16x16, even T >= 8): the tile of the MFMA is ONE image row at TWO timesteps.
+// k_lif_seq_c32d — THE HOT KERNEL (16x16, even T >= 8): the tile of the MFMA is ONE image row at TWO timesteps, and the
+// accumulators are OUTPUT-STATIONARY: a wave keeps its two tiles from the bias to the epilogue.
 //
 // The 32 -> 32 convolution of step t reads only this layer's input traces eps1(t), which depend on the input spikes (in
 // HBM for all T) and not on this layer's output; the only recurrence through the output is the refractory trace, which is
 // elementwise and lives in the epilogue.  So the 32 "pixels" of v_mfma_f32_32x32x2_f32 are: lanes 0..15 image row r at step
-// t, lanes 16..31 the same row at step t + 1, read from two LDS images ("t" and "t+1", TP_IMGP floats apart).  Both halves
+// t, lanes 16..31 the same row at step t + 1, read from two LDS images ("t" and "t+1", OS_IMGP floats apart).  Both halves
 // of the tile have the same tap-row validity, so EVERY tap row that lies in the zero padding is skipped exactly
-// (fmaf(w, +0, acc) == acc): 100 of the 112 (image row, tap row) combinations remain, where the row-paired tiles of
-// k_lif_seq_c32rp keep 104.  Weight fragments, accumulator layout, slot layout and the pinned chain bias -> (cp, ky, kx, h)
-// are those of k_lif_seq_c32.
+// (fmaf(w, +0, acc) == acc): 100 of the 112 (image row, tap row) combinations remain.
 //
-// A step pair takes 8 stages; in its stage s a wave runs the chains of the image rows TP_ROW_A[s] and TP_ROW_B[s].  The four
-// border pairs have 11 live tap rows (154 MFMAs per wave), the four inner ones 14 (196); the order reads 11 11 14 14 11 11 14 14
-// and the two waves of a SIMD are two chain positions apart, so every SIMD carries 350 MFMAs in every stage (364 before).
-// Source row rho is tap row ky = rho - r + 3 of output row r; both chains walk rho upward and share the B fragments.
+// Chain position w owns the image rows TP_ROW_A[w] and TP_ROW_B[w] for the whole sequence and walks the whole chain
+// bias -> (cp = 0..15, ky, kx, h) of both itself: no accumulator ever leaves its wave, there are no slots and no stage
+// barriers.  The border pairs have 11 live tap rows, the inner ones 14, and the two waves of a SIMD are two chain positions
+// apart, so every SIMD carries 25 tap rows = 2800 MFMAs per step pair.  The A fragment of (cp, ky, kx) serves both tiles where
+// ky is a tap row of both; it is streamed from a fragment-ordered copy of the weights ([cp][tap][lane], lane = (h, co):
+// one coalesced 256-byte load per fragment, L2-resident, made by k_c32d_wfrag in front of every launch), into the 7 x 7
+// registers of one channel pair: the fragments of (cp + 1, ky) are requested as soon as the MFMAs of (cp, ky) have issued,
+// six tap rows ahead.  The B fragment is one ds_read_b32 per MFMA, base + immediate, fetched one tap row ahead.
 //
-// The two images are updated IN PLACE: wave w is the only reader and the only writer of channels 4w..4w+3.  At the start of
-// its stage s it advances the image rows 2m, 2m+1 (m = (s + 3) & 7) by two steps — eps1(t+2) from the "t+1" image into the
-// "t" image, eps1(t+3) from that value into the "t+1" image, eps0 in registers: in the stages 0..4 to the step pair the
-// wave is in (no earlier stage of the pair reads these rows), in the stages 5..7 to the next one (no later stage reads
-// them).  tp_schedule_ok() checks that, and the balance above, at compile time.
+// Images: a channel is 16 rows of pitch 19 (3 shared columns of padding, no padding rows: padded tap rows are never
+// read).  Four images — "t" and "t+1" for each parity of the step pair.  In pair p every wave reads the images of parity
+// p & 1 and advances its OWN four channels (eps0, eps1 in registers) to pair p + 1, written into the other parity.  ONE
+// workgroup barrier per step pair orders "all chains of pair p - 1 done" before "writes into that parity" and those writes
+// before the chains of pair p + 1.  The 14-row waves advance their channels BEFORE their chains and the 11-row waves AFTER
+// their epilogue, so that most of the vector work of a SIMD runs under its other wave's MFMAs.
 //
-// Everything a stage indexes registers with is a compile-time function of s = (g - w) & 7 (one switch per stage): the eps0
-// group s, the chain shapes, and the refractory traces of the epilogue share of stage g, which is tile pair (s + w) & 7 —
-// its image row is a scalar.  Epilogue share of wave (wq = w & 3, wpar = w >> 2): quad wq of tile wpar; lane L takes
-// pixel L & 15 and the two channels 8 wq + 4 (L >> 5) + 2 ((L >> 4) & 1) + {0, 1} at BOTH steps (the refractory update of
-// t + 1 needs that of t).  pv / v leave as 64-byte row pieces, the spikes as 16-bit halves of the packed words.
-// DBG (experiments/ablate_c32d.hip only): bit 0 s_memtime stamps of workgroup 0 into v_out, bit 3 chain phase only (no
-// trace update, no epilogue: WRONG results, timing).
+// Epilogue, in the wave: accumulator register i of lane L holds channel (i & 3) + 8 (i >> 2) + 4 (L >> 5) of pixel
+// L & 15 at step t + ((L >> 4) & 1).  One v_permlane16_swap of the registers 2m, 2m + 1 leaves channel
+// 2 (m & 1) + 8 (m >> 1) + 4 h + rb in lane (h, rb, px) at step t in one register and at step t + 1 in the other: the
+// refractory update of t + 1 follows that of t in the same lane, on an arp register the wave keeps for the sequence.
+// pv / v leave as 64-byte row pieces, the spike masks (the compare results) are parked in the lanes of one register and
+// leave as 16-bit halves of the packed words.
+// os_schedule_ok() checks ownership, balance, the parity rule and the LDS budget at compile time.
 // ------------------------------------------------------------------------------------------------------------
-constexpr int TP_IMGP = IMG_FLOATS + 20;    // pitch of the two images: 16 mod 32, the two halves of a B fragment on disjoint banks
-static_assert(TP_IMGP % 32 == 16 && TP_IMGP >= IMG_FLOATS, "image pitch");
 constexpr int TP_ROW_A[8] = {0, 1, 4, 6, 12, 13, 8, 10}, TP_ROW_B[8] = {3, 2, 5, 7, 15, 14, 9, 11};
-constexpr int tp_lo(int r) { return r - 3 < 0 ? 0 : r - 3; }            // first / last source row of output row r
-constexpr int tp_hi(int r) { return r + 3 > 15 ? 15 : r + 3; }
-constexpr int tp_trace_m(int s) { return (s + 3) & 7; }                  // image rows 2m, 2m+1 advanced at the start of stage s
-constexpr bool tp_trace_next(int s) { return s >= 5; }                   // ... to the next step pair (else: to the current one)
-constexpr bool tp_reads(int s, int rho) { return rho >= tp_lo(TP_ROW_A[s]) && rho <= tp_hi(TP_ROW_B[s]); }
-constexpr uint32_t tp_pack(const int (&r)[8])
+constexpr int OS_CHF = 16 * ROWF;                   // a channel: 16 rows, pixel (r, x) at r * 19 + x + 3
+constexpr int OS_IMG = 32 * OS_CHF + 3;             // ... + the right padding of the last row of channel 31
+constexpr int OS_IMGP = 9744;                       // pitch of the images: 16 mod 32, the two halves of a B fragment on disjoint banks
+constexpr int OS_LDS_FLOATS = 4 * OS_IMGP;          // image (parity q, step dt) at (2 q + dt) * OS_IMGP
+constexpr int OS_WFRAG_FLOATS = 16 * 49 * 64;       // the weights in fragment order [cp][tap][lane]
+static_assert(OS_IMGP % 32 == 16 && OS_IMGP >= OS_IMG, "image pitch");
+static_assert(OS_LDS_FLOATS * sizeof(float) <= 160 * 1024, "k_lif_seq_c32d: four eps1 images in 160 KiB of LDS");
+constexpr bool os_tap(int r, int ky) { return r + ky - 3 >= 0 && r + ky - 3 <= 15; }     // is tap row ky of output row r in the image?
+constexpr int os_nky(int w)                         // tap rows that are live for at least one of the wave's tiles
 {
-    uint32_t p = 0;
-    for (int i = 0; i < 8; ++i) p |= (uint32_t)r[i] << (4 * i);
-    return p;
+    int n = 0;
+    for (int ky = 0; ky < 7; ++ky) n += os_tap(TP_ROW_A[w], ky) || os_tap(TP_ROW_B[w], ky);
+    return n;
 }
-constexpr bool tp_schedule_ok()
+constexpr int os_ky(int w, int i)                   // ... the i-th of them
 {
-    int seen = 0, mseen = 0;
-    for (int s = 0; s < 8; ++s) {
-        if (TP_ROW_A[s] >= TP_ROW_B[s]) return false;                   // the union of the source rows is lo(A) .. hi(B)
-        if (tp_lo(TP_ROW_A[s]) > tp_lo(TP_ROW_B[s]) || tp_hi(TP_ROW_A[s]) > tp_hi(TP_ROW_B[s])) return false;
-        if (tp_lo(TP_ROW_B[s]) > tp_hi(TP_ROW_A[s]) + 1) return false;  // ... without a gap
-        seen |= (1 << TP_ROW_A[s]) | (1 << TP_ROW_B[s]);
-        // balance: the partner wave of the SIMD is two chain positions away
-        const int s2 = (s + 2) & 7;
-        const int n = tp_hi(TP_ROW_A[s]) - tp_lo(TP_ROW_A[s]) + tp_hi(TP_ROW_B[s]) - tp_lo(TP_ROW_B[s]) + 2;
-        const int n2 = tp_hi(TP_ROW_A[s2]) - tp_lo(TP_ROW_A[s2]) + tp_hi(TP_ROW_B[s2]) - tp_lo(TP_ROW_B[s2]) + 2;
-        if (n + n2 != 25) return false;
-        // rolling update of rows 2m, 2m+1 at the start of stage s
-        const int m = tp_trace_m(s);
-        mseen |= 1 << m;
-        for (int rho = 2 * m; rho < 2 * m + 2; ++rho) {
-            if (tp_trace_next(s)) {
-                for (int u = s; u < 8; ++u) if (tp_reads(u, rho)) return false;     // still needed at the old steps
-            } else {
-                for (int u = 0; u < s; ++u) if (tp_reads(u, rho)) return false;     // was needed at the new steps
-                if (rho == tp_lo(TP_ROW_A[s])) return false;    // the stage's first B row is fetched before the update
-            }
-        }
+    for (int ky = 0; ky < 7; ++ky)
+        if ((os_tap(TP_ROW_A[w], ky) || os_tap(TP_ROW_B[w], ky)) && i-- == 0) return ky;
+    return -1;
+}
+constexpr int os_rows(int w)                        // live (image row, tap row) combinations of the wave
+{
+    int n = 0;
+    for (int ky = 0; ky < 7; ++ky) n += (os_tap(TP_ROW_A[w], ky) ? 1 : 0) + (os_tap(TP_ROW_B[w], ky) ? 1 : 0);
+    return n;
+}
+constexpr bool os_trace_first(int w) { return os_rows(w) > 12; }        // the long waves advance their channels before their chains
+constexpr int os_read_parity(int p) { return p & 1; }                   // images the chains of pair p read
+constexpr int os_write_parity(int p) { return (p + 1) & 1; }            // images the trace update running in pair p writes (pair p + 1)
+constexpr bool os_schedule_ok()
+{
+    int seen = 0, total = 0;
+    for (int w = 0; w < 8; ++w) {
+        if (seen & ((1 << TP_ROW_A[w]) | (1 << TP_ROW_B[w]))) return false;     // every image row has one owner
+        seen |= (1 << TP_ROW_A[w]) | (1 << TP_ROW_B[w]);
+        total += os_rows(w);
+        // chain position of hardware wave i is (i & 1) | ((i & 4) >> 1) | ((i & 2) << 1): the waves i, i + 4 of a SIMD sit at
+        // positions w, w + 2 with (w & 2) == 0
+        if ((w & 2) == 0 && os_rows(w) + os_rows(w + 2) != 25) return false;
+        if ((w & 2) == 0 && os_trace_first(w) == os_trace_first(w + 2)) return false;
     }
-    return seen == 0xffff && mseen == 0xff;
+    for (int p = 0; p < 4; ++p) {
+        // the update that runs during pair p must not touch what pair p reads, and fills what pair p + 1 reads; what it
+        // overwrites was last read in pair p - 1, which the barrier between p - 1 and p closed
+        if (os_write_parity(p) == os_read_parity(p) || os_write_parity(p) != os_read_parity(p + 1)) return false;
+        if (p > 0 && os_write_parity(p) != os_read_parity(p - 1)) return false;
+    }
+    return seen == 0xffff && total == 100;
 }
-static_assert(tp_schedule_ok(), "k_lif_seq_c32d: tile order / rolling trace schedule");
+static_assert(os_schedule_ok(), "k_lif_seq_c32d: row ownership / SIMD balance / image parity");
 
-template <bool REFRACTORY, int OUT, int DBG = 0>     // OUT bit0: pv, bit1: v
-__global__ __launch_bounds__(512) void k_lif_seq_c32d(const uint32_t *__restrict__ spk_in, const dcll_wsrc W,
+// the weights of a 32 -> 32 7x7 layer in the order k_lif_seq_c32d streams them: [cp][tap][lane], lane = 32 h + co holds
+// W[co][2 cp + h][tap] — through dcll_wsrc::at, so int8 weights dequantise to exactly the values load_wf_c32 produces
+__global__ __launch_bounds__(256) void k_c32d_wfrag(const dcll_wsrc W, float *__restrict__ wfrag)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= OS_WFRAG_FLOATS) return;
+    const int lane = i & 63, f = i >> 6, tap = f % 49, cp = f / 49, co = lane & 31, h = lane >> 5;
+    wfrag[i] = W.at(((long)co * 32 + 2 * cp + h) * 49 + tap, co);
+}
+
+template <bool REFRACTORY, int OUT>     // OUT bit0: pv, bit1: v
+__global__ __launch_bounds__(512) void k_lif_seq_c32d(const uint32_t *__restrict__ spk_in, const float *__restrict__ wfrag,
                                                        const float *__restrict__ bias, const float *__restrict__ tau4,
                                                        float *__restrict__ eps0_g, float *__restrict__ eps1_g,
                                                        float *__restrict__ arp_g, uint32_t *__restrict__ spk_out,
                                                        float *__restrict__ pv_out, float *__restrict__ v_out, int T,
                                                        int B, float alpharp, float wrp)
 {
-    __shared__ __attribute__((aligned(16))) float lds[2 * TP_IMGP + (NWAVE * 2 + 1) * SLOT_FLOATS];
-    float *slots = lds + 2 * TP_IMGP;           // [wave][tile A / B of the pair][16 x 64]
-    float *sbias = slots + NWAVE * 2 * SLOT_FLOATS;     // the bias as a slot-shaped tile: wave 0's chain input
+    __shared__ __attribute__((aligned(16))) float lds[OS_LDS_FLOATS + 32];
+    float *sbias = lds + OS_LDS_FLOATS;         // the bias in accumulator order: [h][register i] = channel (i & 3) + 8 (i >> 2) + 4 h
     const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, j = lane & 31, px = lane & 15, rb = (lane >> 4) & 1;
     // chain position w of hardware wave i: 0 1 4 5 2 3 6 7 — the two waves of a SIMD (i, i + 4) are TWO positions apart
     const int wi = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int w = (wi & 1) | ((wi & 4) >> 1) | ((wi & 2) << 1);
-    const int wq = w & 3, wpar = w >> 2;        // my epilogue share: quad wq of the pair's tile wpar
     const long b = blockIdx.x;
     const int NP = T >> 1;                      // step pairs
     __builtin_amdgcn_s_setprio(3);              // (see k_lif_seq_c32rp)
 
-    for (int i = tid; i < 2 * TP_IMGP; i += 512) lds[i] = 0.0f;
-    // slot layout: float4 c of lane l = accumulator registers 4c..4c+3 = channels (r&3) + 8c + 4(l>>5)
-    for (int i = tid; i < SLOT_FLOATS; i += 512) sbias[i] = bias[(i & 3) + 8 * (i >> 8) + 4 * ((i >> 7) & 1)];
+    for (int i = tid; i < OS_LDS_FLOATS; i += 512) lds[i] = 0.0f;
+    if (tid < 32) sbias[tid] = bias[(tid & 3) + 8 * ((tid >> 2) & 3) + 4 * (tid >> 4)];
 
-    float wf[2][49];
-    load_wf_c32(W, j, w, h, wf);
-
-    // traces: register group s, element e = channel 4w + 2e + h, image row 2 tp_trace_m(s) + rb, pixel px; eps1 in both
-    // images at float offset toff + e*2*CHF + 2m*ROWF
-    float e0[8][2];
-    const int toff = (4 * w + h) * CHF + (rb + 3) * ROWF + px + 3;
-    float ta[2], tm[2], tas[2], ts[2];
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-        ta[e] = tau4[0 * 32 + 4 * w + 2 * e + h]; tm[e] = tau4[1 * 32 + 4 * w + 2 * e + h];
-        tas[e] = tau4[2 * 32 + 4 * w + 2 * e + h]; ts[e] = tau4[3 * 32 + 4 * w + 2 * e + h];
-    }
-    // input spikes: word m of a channel = image rows 2m, 2m+1; the words of channels 2e, 2e+1 side by side ARE the lane mask
-    const uint32_t *in_wave = spk_in + (b * 32 + 4 * w) * 8;
-    const long in_step = (long)B * 32 * 8;
-    auto in_mask = [&](long t, int e, int m) -> unsigned long long {
-        const uint32_t *ip = in_wave + t * in_step + 2 * e * 8 + m;
-        return (unsigned long long)ip[0] | ((unsigned long long)ip[8] << 32);
-    };
     __syncthreads();        // images zeroed
 
-    // prologue: state from HBM, advanced to steps 0 and 1 -> the two images
-    static_for<0, 8>([&](auto SC) {
-        constexpr int S = decltype(SC)::value, M = tp_trace_m(S);
-#pragma unroll
+    // everything below knows its chain position at compile time: one copy per wave of the workgroup
+    auto run = [&](auto WC) {
+        constexpr int W = decltype(WC)::value, RA = TP_ROW_A[W], RB = TP_ROW_B[W], NKY = os_nky(W);
+        constexpr int LO = RA - 3 < 0 ? 0 : RA - 3;             // first source row of the wave (RA < RB)
+        static_assert(RA < RB && ((RB + 3 > 15 ? 15 : RB + 3) - LO) * ROWF + 6 < 256, "B-fragment offsets within ds_read2_b32's range");
+        constexpr bool FIRST = os_trace_first(W);
+        // traces of my channels 4W..4W+3: register group (m, e) = channel 4W + 2e + h, image row 2m + rb, pixel px
+        float e0[8][2], e1[8][2];
+        float ta[2], tm[2], tas[2];
+        uint32_t tsb[2];
+    #pragma unroll
         for (int e = 0; e < 2; ++e) {
-            const long gidx = (b * 32 + 4 * w + 2 * e + h) * 256 + 32 * M + j;
-            e0[S][e] = eps0_g[gidx];
-            float e1 = eps1_g[gidx];
-            float *dst = lds + toff + e * 2 * CHF + 2 * M * ROWF;
-            trace_update((float)((in_mask(0, e, M) >> lane) & 1ull), ta[e], tm[e], tas[e], ts[e], e0[S][e], e1);
-            dst[0] = e1;
-            trace_update((float)((in_mask(1, e, M) >> lane) & 1ull), ta[e], tm[e], tas[e], ts[e], e0[S][e], e1);
-            dst[TP_IMGP] = e1;
+            ta[e] = tau4[0 * 32 + 4 * W + 2 * e + h]; tm[e] = tau4[1 * 32 + 4 * W + 2 * e + h];
+            tas[e] = tau4[2 * 32 + 4 * W + 2 * e + h]; tsb[e] = __float_as_uint(tau4[3 * 32 + 4 * W + 2 * e + h]);
         }
-    });
-    // refractory trace of my epilogue shares: group s = tile pair (s + w) & 7, its tile wpar, channels ech + {0, 1}
-    const uint32_t rowpk = wpar ? tp_pack(TP_ROW_B) : tp_pack(TP_ROW_A);
-    const int ech = 8 * wq + 4 * h + 2 * rb;
-    float arp[8][2];
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-        const int re = (rowpk >> (4 * ((s + w) & 7))) & 15;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) arp[s][k] = REFRACTORY ? arp_g[(b * 32 + ech + k) * 256 + re * 16 + px] : 0.0f;
-    }
-
-    // per-lane base of the B-fragment reads: channel 4w + h, image j >> 4, column j & 15
-    const int bbase = (4 * w + h) * CHF + (j >> 4) * TP_IMGP + (j & 15);
-    // epilogue: my two values of a step in the slot of wave 7, and the lane byte offsets of the stores
-    const int eslot = (7 * 2 + wpar) * SLOT_FLOATS + (wq * 64 + h * 32 + px) * 4 + 2 * rb;
-    const unsigned eoff = 4u * ((4 * h + 2 * rb) * 256 + px);
-    // spike halves: lane px < 4 of every 16 stores the half word of (channel ech + (px & 1), step px >> 1)
-    const unsigned soff = (unsigned)(px >> 1) * ((unsigned)B * 1024u) + 32u * (4 * h + 2 * rb + (px & 1));
-#pragma unroll
-    for (int s = 0; s < 8; ++s)
-#pragma unroll
-        for (int k = 0; k < 2; ++k) asm volatile("" ::"v"(arp[s][k]), "v"(e0[s][k]));
-#pragma unroll
-    for (int cp = 0; cp < 2; ++cp)
-#pragma unroll
-        for (int k = 0; k < 49; ++k) asm volatile("" ::"v"(wf[cp][k]));
-    __syncthreads();
-
-    unsigned long long dbg[4] = {0, 0, 0, 0}, dbg_t0 = 0;       // DBG only: non-MFMA phase, barrier 2, chains, barrier 1
-    if (DBG & 1) dbg_t0 = __builtin_amdgcn_s_memtime();
-    // inputs of the trace share of a wave's next stage (eps1 of the "t+1" image, input masks), fetched one stage ahead
-    float sv[2] = {0.f, 0.f};
-    unsigned long long wm[2][2] = {{0, 0}, {0, 0}};
-    // does the wave advance rows in stage s of its step pair P?  (the prologue did pair 0)
-    auto tracing = [&](const int q, const int s) {
-        const int P = q >> 3;
-        return !(DBG & 8) && q >= 0 && (tp_trace_next(s) ? P + 1 < NP : (P >= 1 && P < NP));
-    };
-    auto fetch_trace_inputs = [&](const int q, auto SC) {
-        constexpr int S = decltype(SC)::value, M = tp_trace_m(S);
-        if (tracing(q, S)) {
-            const long t2 = 2 * ((q >> 3) + (tp_trace_next(S) ? 1 : 0));
-#pragma unroll
+    #pragma unroll
+        for (int m = 0; m < 8; ++m)
+    #pragma unroll
             for (int e = 0; e < 2; ++e) {
-                sv[e] = lds[TP_IMGP + toff + e * 2 * CHF + 2 * M * ROWF];
-                wm[e][0] = in_mask(t2, e, M);
-                wm[e][1] = in_mask(t2 + 1, e, M);
+                const long gidx = (b * 32 + 4 * W + 2 * e + h) * 256 + 32 * m + j;
+                e0[m][e] = eps0_g[gidx];
+                e1[m][e] = eps1_g[gidx];
             }
+        // input spikes of my channels at two steps: word m of a channel = image rows 2m, 2m+1, my pixel is bit j
+        const long in_step = (long)B * 32 * 8;
+        const uint32_t *in_lane = spk_in + (b * 32 + 4 * W + h) * 8;
+        uint32_t mw[2][2][8];
+        auto load_masks = [&](const int t2) {
+    #pragma unroll
+            for (int dt = 0; dt < 2; ++dt)
+    #pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    const uint4 *ip = (const uint4 *)(in_lane + (long)(t2 + dt) * in_step + 2 * e * 8);
+                    const uint4 q0 = ip[0], q1 = ip[1];
+                    mw[dt][e][0] = q0.x; mw[dt][e][1] = q0.y; mw[dt][e][2] = q0.z; mw[dt][e][3] = q0.w;
+                    mw[dt][e][4] = q1.x; mw[dt][e][5] = q1.y; mw[dt][e][6] = q1.z; mw[dt][e][7] = q1.w;
+                }
+        };
+        // my channels two steps on, eps1 into the images of parity par (every op rounded separately)
+        const int toff = (4 * W + h) * OS_CHF + rb * ROWF + px + 3;
+        auto trace = [&](const int par) {
+            float *dst = lds + 2 * par * OS_IMGP + toff;
+    #pragma unroll
+            for (int m = 0; m < 8; ++m)
+    #pragma unroll
+                for (int e = 0; e < 2; ++e)
+    #pragma unroll
+                    for (int dt = 0; dt < 2; ++dt) {
+                        // x * tau_s with x in {0,1}: exact select
+                        const float a = __uint_as_float((uint32_t)__builtin_amdgcn_sbfe((int)mw[dt][e][m], j, 1) & tsb[e]);
+                        const float bb = tas[e] * e0[m][e];
+                        e0[m][e] = a + bb;
+                        const float cc = ta[e] * e1[m][e];
+                        const float dd = e0[m][e] * tm[e];
+                        e1[m][e] = cc + dd;
+                        dst[dt * OS_IMGP + e * 2 * OS_CHF + 2 * m * ROWF] = e1[m][e];
+                    }
+        };
+        load_masks(0);
+        trace(0);               // steps 0, 1
+
+        // per-lane base of the B-fragment reads: channel h of a pair, image j >> 4, column j & 15
+        const int bbase = h * OS_CHF + (j >> 4) * OS_IMGP + (j & 15);
+        // epilogue: lane byte offset of my channel rb + 4h and pixel px within a (step, sample) block of pv / v
+        const unsigned eoff = 4u * ((4 * h + rb) * 256 + px);
+        // spike halves: lane n < 32 holds the mask dword of (register pair n >> 2, step (n >> 1) & 1, lane half n & 1): channel
+        // 2 (m & 1) + 8 (m >> 1) + 4 (n & 1) in its low 16 bits, the next channel in its high ones
+        const unsigned soff = (unsigned)((lane >> 1) & 1) * ((unsigned)B * 1024u) +
+                              32u * (2 * ((lane >> 2) & 1) + 8 * ((lane >> 3) & 3) + 4 * (lane & 1));
+        const auto wrs = tile_rsrc(wfrag);
+        const unsigned wlane = 4u * lane;
+        const f32x4 *bvp = (const f32x4 *)(sbias + 16 * h);
+
+        // refractory traces of my two rows: register m = channel 2 (m & 1) + 8 (m >> 1) + 4 h + rb, pixel px
+        float arpA[8], arpB[8];
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            const long aidx = (b * 32 + 2 * (m & 1) + 8 * (m >> 1) + 4 * h + rb) * 256 + px;
+            arpA[m] = REFRACTORY ? arp_g[aidx + RA * 16] : 0.0f;
+            arpB[m] = REFRACTORY ? arp_g[aidx + RB * 16] : 0.0f;
         }
-    };
-    // one stage; S = (g - w) & 7 at compile time
-    auto stage = [&](const int g, auto SC) {
-        constexpr int S = decltype(SC)::value, RA = TP_ROW_A[S], RB = TP_ROW_B[S];
-        constexpr int LO = tp_lo(RA), HI = tp_hi(RB), NRH = HI - LO + 1, NR = 2 * NRH;
-        unsigned long long st0 = 0, st1 = 0, st2 = 0, st3 = 0;
-        if (DBG & 1) st0 = __builtin_amdgcn_s_memtime();
-        const int q = g - w;
-        const bool active = q >= 0 && q < 8 * NP;
-        // ---- (0) everything this stage reads from LDS goes out first: chain inputs out of the slots ----
-        f32x16 accA, accB;
-        if (active) {
-            const float *inA = (w == 0) ? sbias : slots + ((w - 1) * 2) * SLOT_FLOATS;
-            const float *inB = (w == 0) ? sbias : slots + ((w - 1) * 2 + 1) * SLOT_FLOATS;
-            const f32x4 *spa = (const f32x4 *)inA + lane, *spb = (const f32x4 *)inB + lane;
+        // A fragments of one channel pair; those of cp = 0 now, then always one channel pair ahead
+        float wb[7][7];
+        static_for<0, NKY>([&](auto IC) {
+            constexpr int KY = os_ky(W, decltype(IC)::value);
+#pragma unroll
+            for (int kx = 0; kx < 7; ++kx)
+                wb[KY][kx] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(wrs, wlane, (KY * 7 + kx) * 256, 0));
+        });
+        if (FIRST && NP > 1) load_masks(2);
+        lds_barrier();          // steps 0, 1 of every channel are in the images of parity 0
+
+        for (int p = 0; p < NP; ++p) {
+            if (FIRST && p + 1 < NP) {
+                trace(os_write_parity(p));
+            }
+            // ---- both chains: channel pairs two at a time (the B fragments alternate between two register sets) ----
+            // one base per channel pair of an iteration, at the wave's first source row: every read is base + an offset
+            // below 256 dwords (ds_read2_b32's range — beyond it the compiler rebuilds a base per read)
+            lds_cfloat *ib0 = (lds_cfloat *)(lds + bbase + 2 * os_read_parity(p) * OS_IMGP + LO * ROWF), *ib1 = ib0 + 2 * OS_CHF;
+            asm volatile("" : "+v"(ib0), "+v"(ib1));
+            f32x16 accA, accB;
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                f32x4 va = spa[c * 64], vb = spb[c * 64];
-                accA[4 * c + 0] = va[0]; accA[4 * c + 1] = va[1]; accA[4 * c + 2] = va[2]; accA[4 * c + 3] = va[3];
-                accB[4 * c + 0] = vb[0]; accB[4 * c + 1] = vb[1]; accB[4 * c + 2] = vb[2]; accB[4 * c + 3] = vb[3];
+                const f32x4 q = bvp[c];
+                accA[4 * c + 0] = q[0]; accA[4 * c + 1] = q[1]; accA[4 * c + 2] = q[2]; accA[4 * c + 3] = q[3];
             }
-        }
-        //   epilogue share: my channels of tile wpar of the pair qe = g - 8 that wave 7 finished last stage, both steps
-        const int qe = g - 8;
-        const bool epi = !(DBG & 8) && qe >= 0 && qe < 8 * NP;
-        f32x2 v0 = {0.f, 0.f}, v1 = {0.f, 0.f};
-        if (epi) {
-            v0 = *(const f32x2 *)(slots + eslot);
-            v1 = *(const f32x2 *)(slots + eslot + 64);
-        }
-        //   first B-fragment row of the chains: bases of my two channel pairs as opaque LDS addresses, every read of the
-        //   chains is base + immediate (see k_lif_seq_c32rp)
-        lds_cfloat *ib0 = (lds_cfloat *)(lds + bbase + (LO + 3) * ROWF), *ib1 = (lds_cfloat *)(lds + bbase + (LO + 3) * ROWF + 2 * CHF);
-        asm volatile("" : "+v"(ib0), "+v"(ib1));
-        float bq[2][7];
-        if (active) {
-#pragma unroll
-            for (int kx = 0; kx < 7; ++kx) bq[0][kx] = ib0[kx];
-        }
-        // ---- (2) trace share: rows 2M, 2M+1 of my channels, two steps in place (every op rounded separately) ----
-        if (tracing(q, S)) {
-            float *dst = lds + toff + 2 * tp_trace_m(S) * ROWF;
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                float e1 = sv[e];
-#pragma unroll
-                for (int dt = 0; dt < 2; ++dt) {
-                    float a;                                    // x * tau_s with x in {0,1}: exact select
-                    asm("v_cndmask_b32 %0, 0, %1, %2" : "=v"(a) : "v"(ts[e]), "s"(wm[e][dt]));
-                    const float bb = tas[e] * e0[S][e];
-                    e0[S][e] = a + bb;
-                    const float cc = ta[e] * e1;
-                    const float dd = e0[S][e] * tm[e];
-                    e1 = cc + dd;
-                    dst[e * 2 * CHF + dt * TP_IMGP] = e1;
-                }
-            }
-        }
-        // ---- (1) epilogue share ----
-        if (epi) {
-            const int te = 2 * (qe >> 3);
-            const int re = (rowpk >> (4 * (g & 7))) & 15;       // image row of my tile
-            const long ubase = (((long)te * B + b) * 32 + 8 * wq) * 256, ustep = (long)B * 32 * 256;
-            float vv[2][2];
-            unsigned long long mk[2][2];
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                bool s0, s1;
-                if (REFRACTORY) {
-                    vv[k][0] = refractory(v0[k], arp[S][k], alpharp, wrp, s0);
-                    vv[k][1] = refractory(v1[k], arp[S][k], alpharp, wrp, s1);
-                } else {
-                    vv[k][0] = v0[k]; vv[k][1] = v1[k];
-                    s0 = v0[k] > 0.0f; s1 = v1[k] > 0.0f;
-                }
-                mk[k][0] = __ballot(s0); mk[k][1] = __ballot(s1);
-            }
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt) {
-                const auto prs = tile_rsrc(pv_out + ubase + dt * ustep), vrs = tile_rsrc(v_out + ubase + dt * ustep);
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    if (OUT & 1) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(sigmoidf_dev(vv[k][dt])), prs, eoff + 4u * (k * 256), re * 64, 0);
-                    if (OUT & 2) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(vv[k][dt]), vrs, eoff + 4u * (k * 256), re * 64, 0);
-                }
-            }
-            if (spk_out) {
-                uint32_t myword = 0;
-#pragma unroll
-                for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        const uint32_t mine = h ? (uint32_t)(mk[k][dt] >> 32) : (uint32_t)mk[k][dt];
-                        myword = (px == k + 2 * dt) ? mine : myword;
-                    }
-                myword >>= 16 * rb;
-                if (px < 4)
-                    __builtin_amdgcn_raw_buffer_store_b16((unsigned short)myword, tile_rsrc(spk_out + (ubase >> 5)), soff, 4 * (re >> 1) + 2 * (re & 1), 0);
-            }
-        }
-        if (DBG & 1) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); st1 = __builtin_amdgcn_s_memtime(); }
-        // every slot read of this stage has completed before any wave writes its slots again
-        lds_barrier();
-        if (DBG & 1) st2 = __builtin_amdgcn_s_memtime();
-        // inputs of the NEXT stage's trace share: they land while the chains run (nobody else touches my channels, and my
-        // own update of those rows comes a stage later)
-        fetch_trace_inputs(q + 1, std::integral_constant<int, (S + 1) & 7>{});
-        // ---- (3) my K-slice of both chains: source rows LO..HI per channel pair, row rho is tap row rho - RA + 3 of tile A
-        //      and rho - RB + 3 of tile B where those are taps at all; the next row is fetched before the MFMAs of this one ----
-        if (active) {
-#pragma unroll
-            for (int r = 0; r < NR; ++r) {
-                const int cp = r / NRH, rho = LO + r % NRH;
-                if (r + 1 < NR) {
-                    const int cpn = (r + 1) / NRH, rhon = (r + 1) % NRH;
-#pragma unroll
-                    for (int kx = 0; kx < 7; ++kx) bq[(r + 1) & 1][kx] = (cpn ? ib1 : ib0)[rhon * ROWF + kx];
-                }
-                __builtin_amdgcn_sched_barrier(0);
+            accB = accA;
+            float bqA[2][7], bqB[2][7];
+            auto fetch_b = [&](auto SETC, auto KYC, lds_cfloat *base) {
+                constexpr int SET = decltype(SETC)::value, KY = decltype(KYC)::value;
 #pragma unroll
                 for (int kx = 0; kx < 7; ++kx) {
-                    if (rho >= tp_lo(RA) && rho <= tp_hi(RA))
-                        accA = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[cp][(rho - RA + 3) * 7 + kx], bq[r & 1][kx], accA, 0, 0, 0);
-                    if (rho >= tp_lo(RB) && rho <= tp_hi(RB))
-                        accB = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[cp][(rho - RB + 3) * 7 + kx], bq[r & 1][kx], accB, 0, 0, 0);
+                    if (os_tap(RA, KY)) bqA[SET][kx] = base[(RA + KY - 3 - LO) * ROWF + kx];
+                    if (os_tap(RB, KY)) bqB[SET][kx] = base[(RB + KY - 3 - LO) * ROWF + kx];
                 }
-                __builtin_amdgcn_sched_barrier(0);
-                if (cp == 1 && rho == tp_hi(RA)) {      // tile A is complete, usually while B still runs
-                    f32x4 *dpa = (f32x4 *)(slots + (w * 2) * SLOT_FLOATS) + lane;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c)
-                        dpa[c * 64] = f32x4{accA[4 * c + 0], accA[4 * c + 1], accA[4 * c + 2], accA[4 * c + 3]};
+            };
+            fetch_b(std::integral_constant<int, 0>{}, std::integral_constant<int, os_ky(W, 0)>{}, ib0);
+#pragma nounroll
+            for (int c2 = 0; c2 < 8; ++c2) {
+                const unsigned wnext0 = (unsigned)(2 * c2 + 1) * (49u * 256u), wnext1 = (unsigned)((2 * c2 + 2) & 15) * (49u * 256u);
+                static_for<0, 2 * NKY>([&](auto RC) {
+                    constexpr int R = decltype(RC)::value, CPO = R / NKY, KY = os_ky(W, R % NKY);
+                    if constexpr (R + 1 == NKY) {           // the even channel pair has been fetched: on to the next iteration's
+                        ib0 += 4 * OS_CHF;
+                        asm volatile("" : "+v"(ib0));
+                    }
+                    if constexpr (R + 1 < 2 * NKY)
+                        fetch_b(std::integral_constant<int, (R + 1) & 1>{}, std::integral_constant<int, os_ky(W, (R + 1) % NKY)>{},
+                                (R + 1) / NKY ? ib1 : ib0);
+                    else if (c2 < 7)
+                        fetch_b(std::integral_constant<int, 0>{}, std::integral_constant<int, os_ky(W, 0)>{}, ib0);
                     __builtin_amdgcn_sched_barrier(0);
-                }
+#pragma unroll
+                    for (int kx = 0; kx < 7; ++kx) {
+                        if (os_tap(RA, KY)) accA = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[KY][kx], bqA[R & 1][kx], accA, 0, 0, 0);
+                        if (os_tap(RB, KY)) accB = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[KY][kx], bqB[R & 1][kx], accB, 0, 0, 0);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    // this tap row of the next channel pair (after cp = 15: of cp = 0, for the next step pair)
+                    const unsigned wo = CPO ? wnext1 : wnext0;
+#pragma unroll
+                    for (int kx = 0; kx < 7; ++kx)
+                        wb[KY][kx] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(wrs, wlane, wo + (KY * 7 + kx) * 256, 0));
+                    __builtin_amdgcn_sched_barrier(0);
+                });
+                ib1 += 4 * OS_CHF;
+                asm volatile("" : "+v"(ib1));
             }
-            f32x4 *dp = (f32x4 *)(slots + (w * 2 + 1) * SLOT_FLOATS) + lane;
+            // input spikes of the next trace update (the long waves': that of the next pair), landing under the epilogue
+            if (FIRST ? p + 2 < NP : p + 1 < NP) load_masks(FIRST ? 2 * p + 4 : 2 * p + 2);
+
+            // ---- epilogue of my two rows, both steps ----
+            const long ubase = ((long)(2 * p) * B + b) * 32 * 256, ustep = (long)B * 32 * 256;
+            auto epilogue = [&](f32x16 &acc, float (&arp)[8], auto ROWC) {
+                constexpr int ROW = decltype(ROWC)::value;
+                const auto prs0 = tile_rsrc(pv_out + ubase), prs1 = tile_rsrc(pv_out + ubase + ustep);
+                const auto vrs0 = tile_rsrc(v_out + ubase), vrs1 = tile_rsrc(v_out + ubase + ustep);
+                // (s_nop 1: gfx950 wants two wait states between a VALU write of an SGPR — the compare — and a VALU read of it,
+                // and the compiler does not see into the asm)
+                uint32_t pk = 0;
 #pragma unroll
-            for (int c = 0; c < 4; ++c)
-                dp[c * 64] = f32x4{accB[4 * c + 0], accB[4 * c + 1], accB[4 * c + 2], accB[4 * c + 3]};
+                for (int m = 0; m < 8; ++m) {
+                    // [row0 row1 row2 row3] of 16 lanes: sw[0] = [x.row0 y.row0 x.row2 y.row2] = step t, sw[1] = step t + 1
+                    const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[2 * m]), __float_as_uint(acc[2 * m + 1]), false, false);
+                    float v0 = __uint_as_float(sw[0]), v1 = __uint_as_float(sw[1]);
+                    bool s0, s1;
+                    if (REFRACTORY) {
+                        v0 = refractory(v0, arp[m], alpharp, wrp, s0);
+                        v1 = refractory(v1, arp[m], alpharp, wrp, s1);
+                    } else {
+                        s0 = v0 > 0.0f; s1 = v1 > 0.0f;
+                    }
+                    const unsigned long long mk0 = __ballot(s0), mk1 = __ballot(s1);
+                    const int co = (2 * (m & 1) + 8 * (m >> 1)) * 1024 + ROW * 64;      // byte offset of (channel, row)
+                    if (OUT & 1) {
+                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(sigmoidf_dev(v0)), prs0, eoff, co, 0);
+                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(sigmoidf_dev(v1)), prs1, eoff, co, 0);
+                    }
+                    if (OUT & 2) {
+                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v0), vrs0, eoff, co, 0);
+                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v1), vrs1, eoff, co, 0);
+                    }
+                    asm("s_nop 1\n\tv_writelane_b32 %0, %1, %2" : "+v"(pk) : "s"((uint32_t)mk0), "n"(4 * m + 0));
+                    asm("s_nop 1\n\tv_writelane_b32 %0, %1, %2" : "+v"(pk) : "s"((uint32_t)(mk0 >> 32)), "n"(4 * m + 1));
+                    asm("s_nop 1\n\tv_writelane_b32 %0, %1, %2" : "+v"(pk) : "s"((uint32_t)mk1), "n"(4 * m + 2));
+                    asm("s_nop 1\n\tv_writelane_b32 %0, %1, %2" : "+v"(pk) : "s"((uint32_t)(mk1 >> 32)), "n"(4 * m + 3));
+                }
+                if (spk_out && lane < 32) {
+                    const auto srs = tile_rsrc(spk_out + (ubase >> 5));
+                    __builtin_amdgcn_raw_buffer_store_b16((unsigned short)pk, srs, soff, 4 * (ROW >> 1) + 2 * (ROW & 1), 0);
+                    __builtin_amdgcn_raw_buffer_store_b16((unsigned short)(pk >> 16), srs, soff, 32 + 4 * (ROW >> 1) + 2 * (ROW & 1), 0);
+                }
+            };
+            epilogue(accA, arpA, std::integral_constant<int, RA>{});
+            epilogue(accB, arpB, std::integral_constant<int, RB>{});
+
+            if (!FIRST && p + 1 < NP) trace(os_write_parity(p));
+            // the one barrier of the step pair: every chain of pair p is done before pair p + 1 overwrites its images, and
+            // the images of pair p + 1 are complete before its chains (LDS traffic only, not the pv / spike stores)
+            lds_barrier();
         }
-        if (DBG & 1) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); st3 = __builtin_amdgcn_s_memtime(); }
-        // stage barrier: only the LDS traffic has to be complete, not the pv / spike stores of the epilogue
-        lds_barrier();
-        if (DBG & 1) {
-            const unsigned long long st4 = __builtin_amdgcn_s_memtime();
-            dbg[0] += st1 - st0; dbg[1] += st2 - st1; dbg[2] += st3 - st2; dbg[3] += st4 - st3;
+
+        if (REFRACTORY) {
+            int lo = 4 * h + rb;        // (opaque: the addresses are rebuilt here, not kept in registers over the time loop)
+            asm volatile("" : "+v"(lo));
+#pragma unroll
+            for (int m = 0; m < 8; ++m) {
+                const long aidx = (b * 32 + 2 * (m & 1) + 8 * (m >> 1) + lo) * 256 + px;
+                arp_g[aidx + RA * 16] = arpA[m];
+                arp_g[aidx + RB * 16] = arpB[m];
+            }
         }
+        // state back to HBM: the registers hold steps T - 1
+        int jo = j;                 // (opaque, as above)
+        asm volatile("" : "+v"(jo));
+    #pragma unroll
+        for (int m = 0; m < 8; ++m)
+    #pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const long gidx = (b * 32 + 4 * W + 2 * e + h) * 256 + 32 * m + jo;
+                eps0_g[gidx] = e0[m][e];
+                eps1_g[gidx] = e1[m][e];
+            }
     };
-
-    const int nstage = 8 * NP + 8;
-    for (int g = 0; g < nstage; ++g) {
-        switch ((g - w) & 7) {      // wave-uniform
-        case 0: stage(g, std::integral_constant<int, 0>{}); break;
-        case 1: stage(g, std::integral_constant<int, 1>{}); break;
-        case 2: stage(g, std::integral_constant<int, 2>{}); break;
-        case 3: stage(g, std::integral_constant<int, 3>{}); break;
-        case 4: stage(g, std::integral_constant<int, 4>{}); break;
-        case 5: stage(g, std::integral_constant<int, 5>{}); break;
-        case 6: stage(g, std::integral_constant<int, 6>{}); break;
-        default: stage(g, std::integral_constant<int, 7>{}); break;
-        }
+    switch (w) {        // wave-uniform
+    case 0: run(std::integral_constant<int, 0>{}); break;
+    case 1: run(std::integral_constant<int, 1>{}); break;
+    case 2: run(std::integral_constant<int, 2>{}); break;
+    case 3: run(std::integral_constant<int, 3>{}); break;
+    case 4: run(std::integral_constant<int, 4>{}); break;
+    case 5: run(std::integral_constant<int, 5>{}); break;
+    case 6: run(std::integral_constant<int, 6>{}); break;
+    default: run(std::integral_constant<int, 7>{}); break;
     }
 
-    if ((DBG & 1) && lane == 0 && b == 0) {
-        unsigned long long *dp = (unsigned long long *)v_out + w * 8;       // v_out doubles as the debug buffer
-        dp[0] = __builtin_amdgcn_s_memtime() - dbg_t0;
-        dp[1] = dbg[0]; dp[2] = dbg[1]; dp[3] = dbg[2]; dp[4] = dbg[3];
-    }
-    // state back to HBM: eps1 of the last step T - 1 lives in the "t+1" image
-    static_for<0, 8>([&](auto SC) {
-        constexpr int S = decltype(SC)::value, M = tp_trace_m(S);
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const long gidx = (b * 32 + 4 * w + 2 * e + h) * 256 + 32 * M + j;
-            eps0_g[gidx] = e0[S][e];
-            eps1_g[gidx] = lds[TP_IMGP + toff + e * 2 * CHF + 2 * M * ROWF];
-        }
-    });
-    if (REFRACTORY) {
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            const int re = (rowpk >> (4 * ((s + w) & 7))) & 15;
-#pragma unroll
-            for (int k = 0; k < 2; ++k) arp_g[(b * 32 + ech + k) * 256 + re * 16 + px] = arp[s][k];
-        }
-    }
 }
 
 // readout weights (N, 32*256) [n][co][pix]  ->  epilogue layout [me][wq][n][lane][rr]:
@@ -3930,6 +3921,40 @@ static void launch_c32(int out, int B, hipStream_t st, const uint32_t *spk_in, d
 #undef DCLL_LAUNCH_C32
 }
 
+// Workspace of k_lif_seq_c32d: the fragment-ordered weights of the call in flight, ONE BUFFER PER (device, stream).  Calls on
+// one stream run in order, so the helper of the next call overwrites the copy only after the previous kernel has finished;
+// calls on different streams never share a buffer.  Buffers live as long as the library (200 704 bytes each).  A capturing
+// stream refuses hipMalloc in the default capture mode, so the first call on it allocates in relaxed mode.
+static int c32d_workspace(hipStream_t st, float **out)
+{
+    static std::mutex mu;
+    static std::map<std::pair<int, hipStream_t>, float *> ws;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(DCLL_ERR_LAUNCH, "hipGetDevice failed", "dcll_conv_lif_sequence");
+    }
+    std::lock_guard<std::mutex> guard(mu);
+    const auto key = std::make_pair(dev, st);
+    const auto it = ws.find(key);
+    if (it != ws.end()) {
+        *out = it->second;
+        return DCLL_OK;
+    }
+    void *p = nullptr;
+    hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
+    (void)hipThreadExchangeStreamCaptureMode(&mode);
+    const hipError_t e = hipMalloc(&p, OS_WFRAG_FLOATS * sizeof(float));
+    (void)hipThreadExchangeStreamCaptureMode(&mode);
+    if (e != hipSuccess || !p) {
+        (void)hipGetLastError();
+        return fail(DCLL_ERR_LAUNCH, "no memory for the weight workspace of k_lif_seq_c32d", "dcll_conv_lif_sequence");
+    }
+    ws[key] = (float *)p;
+    *out = (float *)p;
+    return DCLL_OK;
+}
+
 static int dcll_conv_lif_sequence_run(const dcll_conv_desc *d, const uint32_t *spk_in, dcll_wsrc W, const float *b,
                                       const float *tau4, float *eps0, float *eps1, float *arp, uint32_t *spk_out,
                                       float *pv_out, float *v_out, const float *ro_Wp, const float *ro_b,
@@ -3948,7 +3973,7 @@ static int dcll_conv_lif_sequence_run(const dcll_conv_desc *d, const uint32_t *s
         // even T: a tile is one image row at two timesteps (k_lif_seq_c32d); odd T: two image rows at one (k_lif_seq_c32rp)
         const bool tp = (T & 1) == 0;
 #define DCLL_LAUNCH_C32D(K, R, O)                                                                                       \
-    hipLaunchKernelGGL((K<R, O>), dim3(B), dim3(512), 0, st, spk_in, W, b, tau4, eps0, eps1, arp, spk_out, pv_out,      \
+    hipLaunchKernelGGL((K<R, O>), dim3(B), dim3(512), 0, st, spk_in, WSRC, b, tau4, eps0, eps1, arp, spk_out, pv_out,   \
                        v_out, T, B, d->alpharp, d->wrp)
 #define DCLL_LAUNCH_C32D_O(K, R)                                                                                        \
     switch (out) {                                                                                                     \
@@ -3958,9 +3983,21 @@ static int dcll_conv_lif_sequence_run(const dcll_conv_desc *d, const uint32_t *s
     default: DCLL_LAUNCH_C32D(K, R, 3); break;                                                                         \
     }
         if (tp) {
+            // the weights of THIS call in fragment order, in the launch stream's workspace (they may have changed since the
+            // last call: nothing is kept).  The helper is not a layer launch: no note in the launch log, its own check.
+            float *WSRC = nullptr;
+            const int rc = c32d_workspace(st, &WSRC);
+            if (rc) return rc;
+            hipLaunchKernelGGL(k_c32d_wfrag, dim3(OS_WFRAG_FLOATS / 256), dim3(256), 0, st, W, WSRC);
+            const hipError_t eh = hipGetLastError();
+            if (eh != hipSuccess) {
+                snprintf(dcll_err_buf(), DCLL_ERR_LEN, "k_c32d_wfrag: %s", hipGetErrorString(eh));
+                return DCLL_ERR_LAUNCH;
+            }
             if (d->refractory) { DCLL_LAUNCH_C32D_O(k_lif_seq_c32d, true) } else { DCLL_LAUNCH_C32D_O(k_lif_seq_c32d, false) }
             HIP_CHECK_LAUNCH("k_lif_seq_c32d");
         } else {
+            const dcll_wsrc WSRC = W;
             if (d->refractory) { DCLL_LAUNCH_C32D_O(k_lif_seq_c32rp, true) } else { DCLL_LAUNCH_C32D_O(k_lif_seq_c32rp, false) }
             HIP_CHECK_LAUNCH("k_lif_seq_c32rp");
         }
