@@ -604,6 +604,67 @@ int dcll_conv_lif_step_any(const dcll_conv_desc *d, const float *x, const float 
                            const float *i2o_W, const float *i2o_b, const float *out_W, const float *out_b, float *out_s,
                            float *out_p, float *out_o, float *out_pv, float *out_v, float *w_scratch, int32_t B, void *stream);
 
+/*
+ * Added under ABI 10 (DCLL_ABI_VERSION is unchanged: a caller detects these two symbols by symbol lookup) — one layer step of a
+ * (1,3) / 64-channel / (1,2)-pool layer of radio_ml_conv_ref.yaml in one MFMA launch (k_lif_step_w3, csrc/dcll_step_w3.hip):
+ * dcll_conv_lif_step_any's arguments without w_scratch, dcll_conv_lif_step's results.  Additions only: the default dispatch, its
+ * launch logs and every refusal of the existing entry points are unchanged.
+ * Served (else DCLL_ERR_UNSUPPORTED, before any launch) — exactly the layers the fused sequence kernel k_lif_seq_w3 serves: c_in 1
+ * or 64, c_out 64, kernel (1,3), padding (0,1), pooling (1,2), w a power of two <= 256, h w % 32 == 0, h w < 2^24, stride =
+ * dilation = groups = 1.  dcll_conv_lif_step_w3_lds returns the LDS bytes of a workgroup of the larger form,
+ *   4 x ((256 + 256 / w + 1) x (c_in == 64 ? 65 : 1) + 64),
+ * and 0 for a descriptor that is not served (invalid ones included); the launcher checks each launch against it.
+ * DCLL_ERR_INVALID, before any launch: a NULL required pointer, a refractory layer without arp, an output layer without out_W /
+ * out_o, B < 0, B h w / 32 beyond 2^31 - 9.  B == 0: DCLL_OK, nothing is looked at.  Nothing is allocated, nothing synchronises.
+ * As dcll_conv_lif_step_any: dense fp32 x of any values; fp32 weights only, read from W on every call (the learning step changes
+ * them between any two calls: no permuted copy is kept); b may be NULL; scalar or (c_in,h,w) time constants; eps0 / eps1 / arp
+ * updated in place; out_v (un-pooled) may be NULL; p / o through the same readout kernels.  Pointers need 4-byte alignment only.
+ * Arithmetic: the contract at the top of this file — every v is ONE fmaf chain from b[co] over (cp, kx, h), ci = 2 cp + h, on
+ * v_mfma_f32_32x32x2_f32 (c_in = 1: three fmaf, kx = 0, 1, 2).  v equals dcll_conv_lif_step bit for bit up to the sign of a zero;
+ * pooled spikes, eps0, eps1 and arp bit for bit; pv within the sigmoid's 1e-4.
+ * Forms (the launch log names them; R = refractory): a 512-thread workgroup owns 8 or 4 consecutive 32-pixel tiles of the
+ * flattened planes and advances their traces in place, so it must own whole rows (32 x tiles % w == 0):
+ *   "k_lif_step_w3<R> (8 tiles)"             c_in 64
+ *   "k_lif_step_w3<R> (4 tiles)"             c_in 64, w <= 128 and ceil(B h w / 256) < 256 (fewer 8-tile workgroups than CUs)
+ *   "k_lif_step_w3<R> (c_in 1, 8 tiles)"     first layer, the chain on the vector pipe
+ *   "k_lif_step_w3<R> (c_in 1, 4 tiles)"     the same rule
+ * Results do not depend on the form.
+ */
+int64_t dcll_conv_lif_step_w3_lds(const dcll_conv_desc *d);
+int dcll_conv_lif_step_w3(const dcll_conv_desc *d, const float *x, const float *W, const float *b, const float *alpha,
+                          const float *tau_m, const float *alphas, const float *tau_s, float *eps0, float *eps1, float *arp,
+                          const float *i2o_W, const float *i2o_b, const float *out_W, const float *out_b, float *out_s,
+                          float *out_p, float *out_o, float *out_pv, float *out_v, int32_t B, void *stream);
+
+/*
+ * Added under ABI 10 (DCLL_ABI_VERSION is unchanged: a caller detects these three symbols by symbol lookup) — the backward of a
+ * layer of that geometry with the weight gradient of its 64 -> 64 form as an fp32-MFMA GEMM (k_bwd_wgrad_w3,
+ * csrc/dcll_step_w3.hip): arguments, results and scratch rule of dcll_conv_lif_backward / dcll_conv_lif_backward_open
+ * (scratch_floats >= B 64 h w + k x 64 (3 c_in + 1), k >= 1 partial rows; at most 256 are used).  dv comes from the existing
+ * k_bwd_dv, the output_ gradient from the existing kernels; dcll_conv_lif_backward and its launch logs are unchanged.
+ * Served: the layers dcll_conv_lif_step_w3 serves (else DCLL_ERR_UNSUPPORTED before any launch).  dcll_conv_lif_backward_w3_lds
+ * returns the LDS bytes of the weight-gradient kernel's workgroup — c_in 64: 4 x (64 CS + 64 x 129 + 16), CS = the positions of a
+ * 128-pixel block (128 + 128 / w + 1; w = 256: 130) rounded up to 3 mod 32, at most 83 008 (w = 2) — and 0 for a descriptor that is
+ * not served; the launcher checks each launch against it.
+ * DCLL_ERR_INVALID, before any launch: a NULL required pointer, v == NULL (these layers always pool), a scratch too small for one
+ * partial row, B < 0.  B == 0: DCLL_OK, nothing is looked at.
+ * Launch log: "k_bwd_dv", then "k_bwd_wgrad_w3" (c_in 64) or the generic "k_bwd_wgrad" (c_in 1: 3 + 1 columns are not matrix
+ * work; the entry point keeps the default kernel for it), then the reduction / output_ gradient kernels of dcll_conv_lif_backward.
+ * Sums: chunk c takes the 128-pixel blocks c, c + nchunk, ... of the flattened (B x h w) pixels in order; inside a block the
+ * pixel pairs [0, 32) and [32, 64) run as two fma chains (pixel 2 pp, then 2 pp + 1) that are added, first + second, at the end;
+ * the chunks are reduced by k_bwd_reduce[4] / dcll_grad_reduce_adam.  Every order is fixed: two runs give the same bits, and
+ * _open + dcll_grad_reduce_adam gives the closed form's.  NOT bit-identical to dcll_conv_lif_backward: the order differs.
+ */
+int64_t dcll_conv_lif_backward_w3_lds(const dcll_conv_desc *d);
+int dcll_conv_lif_backward_w3(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                              const float *g_p, const float *g_o, const float *g_pv, const float *g_v, const float *i2o_W,
+                              float *dW, float *db, float *d_outW, float *d_outb, float *scratch, int64_t scratch_floats,
+                              int32_t B, void *stream);
+int dcll_conv_lif_backward_w3_open(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                                   const float *g_p, const float *g_o, const float *g_pv, const float *g_v, const float *i2o_W,
+                                   float *d_outW, float *d_outb, float *scratch, int64_t scratch_floats, int32_t B,
+                                   const float **part, int32_t *nchunk, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3301,6 +3301,40 @@ extern "C" int dcll_conv_lif_step_any(const dcll_conv_desc *d, const float *x, c
     return DCLL_OK;
 }
 
+// added under ABI 10: the layer step of a (1,3) / 64-channel / (1,2)-pool layer on k_lif_step_w3 (dcll_step_w3.hip) — one
+// launch, then the readouts of dcll_conv_lif_step.  Every check — the launcher's form, grid and LDS checks and its LDS
+// reservation included — comes before the first launch; behind it only a launch itself can fail.
+extern "C" int dcll_conv_lif_step_w3(const dcll_conv_desc *d, const float *x, const float *W, const float *b,
+                                     const float *alpha, const float *tau_m, const float *alphas, const float *tau_s,
+                                     float *eps0, float *eps1, float *arp, const float *i2o_W, const float *i2o_b,
+                                     const float *out_W, const float *out_b, float *out_s, float *out_p, float *out_o,
+                                     float *out_pv, float *out_v, int32_t B, void *stream)
+{
+    const char *who = "dcll_conv_lif_step_w3";
+    if (B < 0) return fail(DCLL_ERR_INVALID, "negative batch", who);
+    if (B == 0) return DCLL_OK;
+    int rc = dcll_step_w3_check(d, who);
+    if (rc) return rc;
+    if (!x || !W || !alpha || !tau_m || !alphas || !tau_s || !eps0 || !eps1 || !out_s || !out_pv)
+        return fail(DCLL_ERR_INVALID, "null pointer", who);
+    if (d->refractory && !arp) return fail(DCLL_ERR_INVALID, "refractory layer needs arp", who);
+    if (d->output_layer && (!out_W || !out_o)) return fail(DCLL_ERR_INVALID, "output layer needs out_W and out_o", who);
+    hipStream_t st = (hipStream_t)stream;
+    int ch, cw, ph, pw;
+    conv_shape(d, &ch, &cw, &ph, &pw);
+    const int K = d->c_out * ph * pw;
+    const int nt = dcll_step_w3_tiles(d, B);
+    // (one call: the launcher's checks all precede its one launch, and nothing is launched in front of it)
+    rc = dcll_launch_step_w3(d, x, W, b, alpha, tau_m, alphas, tau_s, eps0, eps1, arp, out_s, out_pv, out_v, nt, B, st, true);
+    if (rc) return rc;
+    if (i2o_W && out_p) {
+        rc = launch_readout(out_pv, i2o_W, i2o_b, out_p, B, K, d->target, st);
+        if (rc) return rc;
+    }
+    if (d->output_layer) return launch_readout(out_pv, out_W, out_b, out_o, B, K, d->target, st);
+    return DCLL_OK;
+}
+
 extern "C" int dcll_dense_lif_step(const dcll_dense_desc *d, const float *x, const float *W, const float *b,
                                    const float *alpha, const float *tau_m, const float *alphas, const float *tau_s,
                                    float *eps0, float *eps1, float *arp, const float *i2o_W, const float *i2o_b,
@@ -3489,16 +3523,22 @@ __global__ __launch_bounds__(256) void k_bwd_outgrad_mfma(const float *__restric
     }
 }
 
+// the weight-gradient kernel of a backward call: the default dispatch, or one of the opt-in entry points' kernels
+enum wgrad_sel { WGRAD_DEFAULT, WGRAD_ANY, WGRAD_W3 };
+
 // open_part != nullptr: the weight gradient's partial rows are left in scratch (*open_part, *open_nchunk) for
 // dcll_grad_reduce_adam; dW / db are not written
 static int conv_lif_backward_impl(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
                                   const float *g_p, const float *g_o, const float *g_pv, const float *g_v,
                                   const float *i2o_W, float *dW, float *db, float *d_outW, float *d_outb,
                                   float *scratch, int64_t scratch_floats, int32_t B, void *stream,
-                                  const float **open_part, int32_t *open_nchunk, bool dv_done = false, bool any = false)
+                                  const float **open_part, int32_t *open_nchunk, bool dv_done = false,
+                                  wgrad_sel sel = WGRAD_DEFAULT)
 {
-    // any: the weight gradient by k_bwd_wgrad_any (dcll_bwd_any.hip) whatever the geometry — none of the specialised
-    // kernels, and neither the tap nor the row-width limit of the generic k_bwd_wgrad
+    // WGRAD_ANY: the weight gradient by k_bwd_wgrad_any (dcll_bwd_any.hip) whatever the geometry — none of the specialised
+    // kernels, and neither the tap nor the row-width limit of the generic k_bwd_wgrad.  WGRAD_W3: by k_bwd_wgrad_w3
+    // (dcll_step_w3.hip) for the 64 -> 64 layers of the (1,3) geometry; its first layer (c_in 1) keeps the dispatch below
+    const bool any = sel == WGRAD_ANY, w3 = sel == WGRAD_W3;
     int rc = check_desc(d);
     if (rc) return rc;
     const bool nopool = d->pool_h == 1 && d->pool_w == 1 && d->target <= 32;
@@ -3517,6 +3557,15 @@ static int conv_lif_backward_impl(const dcll_conv_desc *d, const float *eps1, co
         if ((rc = dcll_bwd_wgrad_any_check(d, "dcll_conv_lif_backward_any")) != DCLL_OK) return rc;
         if (scratch_floats < nconv + (long)d->c_out * ((long)d->c_in * d->kh * d->kw + 1))
             return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward_any: scratch too small (need B*c_out*ch*cw + k*(c_out*(c_in*kh*kw+1)), k >= 1)");
+    }
+    if (w3) {       // likewise
+        if ((rc = dcll_bwd_w3_check(d, "dcll_conv_lif_backward_w3")) != DCLL_OK) return rc;
+        if (scratch_floats < nconv + (long)d->c_out * ((long)d->c_in * 3 + 1))
+            return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward_w3: scratch too small (need B*c_out*h*w + k*(c_out*(c_in*3+1)), k >= 1)");
+        if (d->c_in == 64) {        // (the launcher's own checks and its LDS reservation, nothing launched)
+            long nc = (scratch_floats - nconv) / ((long)d->c_out * ((long)d->c_in * 3 + 1));
+            if ((rc = dcll_launch_bwd_wgrad_w3(d, scratch, eps1, scratch + nconv, B, &nc, st, false)) != DCLL_OK) return rc;
+        }
     }
     const char *dv_form = "k_bwd_dv";        // (the generic kernel: pooling, or more than 32 readout rows)
     if (dv_done) {
@@ -3552,6 +3601,8 @@ static int conv_lif_backward_impl(const dcll_conv_desc *d, const float *eps1, co
     const bool c32 = d->c_in == 32 && d->c_out == 32 && d->kh == 7 && d->kw == 7 && d->pad_h == 3 && d->pad_w == 3 && plain_conv(d);
     if (any) {
         if ((rc = dcll_launch_bwd_wgrad_any(d, scratch, eps1, part, B, &nchunk, st)) != DCLL_OK) return rc;
+    } else if (w3 && d->c_in == 64) {
+        if ((rc = dcll_launch_bwd_wgrad_w3(d, scratch, eps1, part, B, &nchunk, st, true)) != DCLL_OK) return rc;
     } else if (c32 && d->h == 16 && d->w == 16) {
         if (nchunk > 256) nchunk = 256;
         if (nchunk > B) nchunk = B;
@@ -3680,7 +3731,7 @@ extern "C" int dcll_conv_lif_backward_any(const dcll_conv_desc *d, const float *
                                           float *scratch, int64_t scratch_floats, int32_t B, void *stream)
 {
     return conv_lif_backward_impl(d, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, dW, db, d_outW, d_outb, scratch,
-                                  scratch_floats, B, stream, nullptr, nullptr, false, true);
+                                  scratch_floats, B, stream, nullptr, nullptr, false, WGRAD_ANY);
 }
 
 extern "C" int dcll_conv_lif_backward_any_open(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
@@ -3690,7 +3741,30 @@ extern "C" int dcll_conv_lif_backward_any_open(const dcll_conv_desc *d, const fl
 {
     if (!part || !nchunk) return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward_any_open: null part / nchunk");
     return conv_lif_backward_impl(d, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, nullptr, nullptr, d_outW, d_outb, scratch,
-                                  scratch_floats, B, stream, part, nchunk, false, true);
+                                  scratch_floats, B, stream, part, nchunk, false, WGRAD_ANY);
+}
+
+// added under ABI 10: the same two calls with the weight gradient of a 64 -> 64 layer of the (1,3) / (1,2)-pool geometry on
+// k_bwd_wgrad_w3 (dcll_step_w3.hip; dcll_conv_lif_backward_w3_lds is the predicate).  B == 0: DCLL_OK, nothing is looked at
+extern "C" int dcll_conv_lif_backward_w3(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                                         const float *g_p, const float *g_o, const float *g_pv, const float *g_v,
+                                         const float *i2o_W, float *dW, float *db, float *d_outW, float *d_outb,
+                                         float *scratch, int64_t scratch_floats, int32_t B, void *stream)
+{
+    if (B == 0) return DCLL_OK;
+    return conv_lif_backward_impl(d, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, dW, db, d_outW, d_outb, scratch,
+                                  scratch_floats, B, stream, nullptr, nullptr, false, WGRAD_W3);
+}
+
+extern "C" int dcll_conv_lif_backward_w3_open(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                                              const float *g_p, const float *g_o, const float *g_pv, const float *g_v,
+                                              const float *i2o_W, float *d_outW, float *d_outb, float *scratch,
+                                              int64_t scratch_floats, int32_t B, const float **part, int32_t *nchunk, void *stream)
+{
+    if (B == 0) return DCLL_OK;
+    if (!part || !nchunk) return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward_w3_open: null part / nchunk");
+    return conv_lif_backward_impl(d, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, nullptr, nullptr, d_outW, d_outb, scratch,
+                                  scratch_floats, B, stream, part, nchunk, false, WGRAD_W3);
 }
 
 // dcll_conv_lif_backward_open for n layers — the slices of one learning timestep — with their dv launches as ONE launch

@@ -171,6 +171,24 @@ int dcll_launch_step_any(const dcll_conv_desc *d, const float *x, const float *w
                          const float *tau_m, const float *alphas, const float *tau_s, float *eps0, float *eps1, float *arp,
                          float *out_s, float *out_pv, float *out_v, int ns, int32_t B, hipStream_t st, bool launch);
 
+// k_lif_step_w3 (dcll_step_w3.hip): one MFMA layer step of the layers dcll_seq_w3_geometry() serves.  _check: DCLL_OK or the
+// refusal with its message; _tiles: tiles per workgroup (8 or 4) for (descriptor, B); the launcher with launch == false only
+// prepares (checks, LDS reservation): called before the first launch of the entry point
+__attribute__((visibility("hidden"))) int dcll_step_w3_check(const dcll_conv_desc *d, const char *who);
+__attribute__((visibility("hidden"))) int dcll_step_w3_tiles(const dcll_conv_desc *d, int32_t B);
+__attribute__((visibility("hidden")))
+int dcll_launch_step_w3(const dcll_conv_desc *d, const float *x, const float *W, const float *b, const float *alpha,
+                        const float *tau_m, const float *alphas, const float *tau_s, float *eps0, float *eps1, float *arp,
+                        float *out_s, float *out_pv, float *out_v, int nt, int32_t B, hipStream_t st, bool launch);
+
+// k_bwd_wgrad_w3 (dcll_step_w3.hip): MFMA weight gradient of the 64 -> 64 layers of that geometry.  _check: DCLL_OK or the
+// refusal; the launcher caps *nchunk (partial rows there is room for) and returns it; launch == false: checks and the LDS
+// reservation only
+__attribute__((visibility("hidden"))) int dcll_bwd_w3_check(const dcll_conv_desc *d, const char *who);
+__attribute__((visibility("hidden")))
+int dcll_launch_bwd_wgrad_w3(const dcll_conv_desc *d, const float *gvf, const float *eps1, float *part, int32_t B,
+                             long *nchunk, hipStream_t st, bool launch);
+
 // dense twins (dcll_dense.hip): one step as an fp32-MFMA GEMM on the updated traces; all T steps with the state on chip
 __attribute__((visibility("hidden")))
 int dcll_launch_dense_mfma(const dcll_dense_desc *d, const float *eps1, const float *W, const float *b, float *arp,

@@ -286,10 +286,13 @@ class ContinuousConv2D(nn.Module):
     # ConvNetwork.any_step_path, which asks step_any_supported() first; set here directly, a layer the library refuses (or one
     # given int8 weights afterwards) raises DCLLUnsupported / ValueError from every step — there is no fall-back
     any_step_path = False
+    # _step: dcll_conv_lif_step_w3 (k_lif_step_w3) instead; opt-in through ConvNetwork.w3_step_path, which asks
+    # w3_step_supported() first.  Set here directly the same holds: a layer the library refuses raises, there is no fall-back
+    w3_step_path = False
 
     def _step(self, input, pooling=(1, 1), i2o=None, output_=None, out=None, stacked=None, finish=None, want_v=True,
               defer_ro=False):
-        """Run one step through dcll_conv_lif_step (any_step_path: dcll_conv_lif_step_any); returns (s_pooled, p, o, pv_pooled,
+        """Run one step through dcll_conv_lif_step (any_step_path: dcll_conv_lif_step_any; w3_step_path: dcll_conv_lif_step_w3); returns (s_pooled, p, o, pv_pooled,
         v).  `out`: optional dict of reusable output buffers; `stacked` / `finish` / `defer_ro`: the fused readout tail of the
         step (ops.conv_lif_step)."""
         self._check_batch(input)
@@ -304,7 +307,7 @@ class ContinuousConv2D(nn.Module):
                 None if i2o is None else i2o.weight, None if i2o is None else i2o.bias,
                 None if output_ is None else output_.weight, None if output_ is None else output_.bias, out=out,
                 q8=self.int8_weights(), stacked=stacked, finish=finish, want_v=want_v, defer_ro=defer_ro,
-                any_path=self.any_step_path)
+                any_path=self.any_step_path, w3_path=self.w3_step_path)
 
     def _general(self):
         """True when the layer was built with an option outside the fused step (see _is_sigmoid)."""
@@ -694,6 +697,17 @@ class Conv2dDCLLlayer(nn.Module):
         if i._general() or i.int8_weights() is not None:
             return False
         return ops.step_any_supported(i.make_desc(self.im_dims, self.pooling, self.target_size, self.output_layer))
+
+    # -- the MFMA per-step forward and weight gradient of the (1,3) / 64-channel layers (k_lif_step_w3, k_bwd_wgrad_w3) ------
+    def w3_step_supported(self):
+        """True if dcll_conv_lif_step_w3 and dcll_conv_lif_backward_w3 serve this layer: built inside the fused step (not
+        _general()), fp32 weights (no int8 form) and the library's predicates (c_in 1 or 64, c_out 64, kernel (1,3), padding
+        (0,1), pooling (1,2), w a power of two <= 256, h * w % 32 == 0 — ops.step_w3_supported / backward_w3_supported)."""
+        i = self.i2h
+        if i._general() or i.int8_weights() is not None:
+            return False
+        desc = i.make_desc(self.im_dims, self.pooling, self.target_size, self.output_layer)
+        return ops.step_w3_supported(desc) and ops.backward_w3_supported(desc)
 
     # -- the fused path of any plain conv layer (k_lif_seq_any, ABI 8): opt-in, beside sequence_kind / forward_sequence ---
     def sequence_any_supported(self):
@@ -1151,6 +1165,14 @@ class DCLLBase(nn.Module):
     # -- the MFMA weight gradient of any plain conv layer (k_bwd_wgrad_any, ABI 9): opt-in, beside the default dispatch ------
     any_learning_path = False       # _learn_tail: dcll_conv_lif_backward_any[_open] instead of dcll_conv_lif_backward[_open]
 
+    w3_learning_path = False        # _learn_tail: dcll_conv_lif_backward_w3[_open] (k_bwd_wgrad_w3); set by ConvNetwork.w3_step_path
+
+    def w3_step_supported(self):
+        """True if this slice's layer steps and backward can run on k_lif_step_w3 / k_bwd_wgrad_w3
+        (Conv2dDCLLlayer.w3_step_supported)."""
+        L = self.dclllayer
+        return isinstance(L, Conv2dDCLLlayer) and L.w3_step_supported()
+
     def backward_any_supported(self):
         """True if this slice's native learning step can take its weight gradient from k_bwd_wgrad_any: a Conv2dDCLLlayer built
         inside the fused step (not _general()) that the library's predicate serves (plain conv, c_out <= 32, kernel up to 16x16,
@@ -1176,7 +1198,7 @@ class DCLLBase(nn.Module):
         dcll_conv_lif_backward into the parameters' .grad.  `open_reduce`: the weight gradient's last reduction is left to
         the caller's ops.grad_reduce_adam (self._learn_bufs['grads']['parts']); `defer_backward` (a list, with open_reduce): the
         backward is not launched here but appended for ops.conv_lif_backward_open_multi (all slices' dv in one launch) — with
-        any_learning_path the slice's own open call is launched at once instead.
+        any_learning_path or w3_learning_path the slice's own open call is launched at once instead.
         -> loss (1,) device tensor or None"""
         L = self.dclllayer
         i2h = L.i2h
@@ -1209,7 +1231,8 @@ class DCLLBase(nn.Module):
                 gb.update(d_outW=prm[2].grad, d_outb=prm[3].grad)
             ops.conv_lif_backward(desc, i2h.state.eps1, v, pv, g_p, g_o, None, None, L.i2o.weight,
                                   want_out=L.output_layer, out=gb, open_reduce=open_reduce,
-                                  defer=defer_backward if open_reduce else None, any_path=self.any_learning_path)
+                                  defer=defer_backward if open_reduce else None, any_path=self.any_learning_path,
+                                  w3_path=self.w3_learning_path)
         return loss
 
     def _grads_into_slab(self):

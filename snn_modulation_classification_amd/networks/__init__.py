@@ -307,6 +307,7 @@ class ConvNetwork(torch.nn.Module):
             walk(s.__dict__.get('_learn_bufs', {}))
             sig.append(bool(s.any_learning_path))
             sig.append(bool(L.i2h.any_step_path))
+            sig.append((bool(s.w3_learning_path), bool(L.i2h.w3_step_path)))
             for t in s._adam_tensors(advance=False):
                 sig += [t['param'].data_ptr(), t['grad'].data_ptr(), t['exp_avg'].data_ptr(),
                         t['exp_avg_sq'].data_ptr(), t['weight_decay'], t['beta1'], t['beta2'], t['eps']]
@@ -528,6 +529,7 @@ class ConvNetwork(torch.nn.Module):
             q8 = L.i2h.int8_weights()            # (a capture taken on the int8 form must not outlive it)
             sig.append(None if q8 is None else (q8[0].data_ptr(), q8[1].data_ptr()))
             sig.append(bool(L.i2h.any_step_path))
+            sig.append(bool(L.i2h.w3_step_path))
         return tuple(sig)
 
     @torch.no_grad()
@@ -877,6 +879,8 @@ class ConvNetwork(torch.nn.Module):
     @any_learning_path.setter
     def any_learning_path(self, on):
         on = bool(on)
+        if on and self.w3_step_path:
+            raise ops._lib.DCLLUnsupported('any_learning_path cannot be combined with w3_step_path')
         if on and not self.backward_any_supported():
             raise ops._lib.DCLLUnsupported('dcll_conv_lif_backward_any does not serve every layer of this network')
         for s in self.dcll_slices:
@@ -899,10 +903,43 @@ class ConvNetwork(torch.nn.Module):
     @any_step_path.setter
     def any_step_path(self, on):
         on = bool(on)
+        if on and self.w3_step_path:
+            raise ops._lib.DCLLUnsupported('any_step_path cannot be combined with w3_step_path')
         if on and not self.step_any_supported():
             raise ops._lib.DCLLUnsupported('dcll_conv_lif_step_any does not serve every layer of this network')
         for s in self.dcll_slices:
             s.dclllayer.i2h.any_step_path = on  # (part of _graph_signature and _test_signature: a capture of the other path is retaken)
+
+    # -- the MFMA learning step of the (1,3) / 64-channel layers of radio_ml_conv_ref.yaml: opt-in, beside the default dispatch --
+    def w3_step_supported(self):
+        """True if every layer's steps and backward are served by dcll_conv_lif_step_w3 / dcll_conv_lif_backward_w3
+        (Conv2dDCLLlayer.w3_step_supported): radio_ml_conv_ref.yaml at netscale 1 with fp32 weights, on planes whose width is a
+        power of two <= 256 and stays >= 2 through the poolings."""
+        return all(s.w3_step_supported() for s in self.dcll_slices)
+
+    @property
+    def w3_step_path(self):
+        """True: every per-step layer call — net.test(x[t]), every learning timestep, Conv2dDCLLlayer.forward — runs
+        k_lif_step_w3 (traces, fp32-MFMA chains and the (1,2) pooling in one launch) instead of dcll_conv_lif_step's k_trace +
+        k_conv_lif_tiled<1,3> + k_pool, and every learning step takes the weight gradient of its 64 -> 64 layers from
+        k_bwd_wgrad_w3 instead of k_bwd_wgrad.  One switch for both halves.  The readout tails and the sequence calls
+        (test_sequence, the burn-in of learn_sequence) are untouched.  Default False; setting it on a network with a layer that
+        is not served (other geometry, int8 weights, netscale != 1, general-option layers) or together with any_step_path /
+        any_learning_path raises DCLLUnsupported and leaves it off; switching it off is always allowed."""
+        return all(s.w3_learning_path and s.dclllayer.i2h.w3_step_path for s in self.dcll_slices)
+
+    @w3_step_path.setter
+    def w3_step_path(self, on):
+        on = bool(on)
+        if on and (any(s.any_learning_path for s in self.dcll_slices) or
+                   any(s.dclllayer.i2h.any_step_path for s in self.dcll_slices)):
+            raise ops._lib.DCLLUnsupported('w3_step_path cannot be combined with any_step_path / any_learning_path')
+        if on and not self.w3_step_supported():
+            raise ops._lib.DCLLUnsupported('dcll_conv_lif_step_w3 / dcll_conv_lif_backward_w3 do not serve every layer of this '
+                                           'network')
+        for s in self.dcll_slices:              # (part of _graph_signature and _test_signature: a capture of the other path is retaken)
+            s.w3_learning_path = on
+            s.dclllayer.i2h.w3_step_path = on
 
     # -- the fused path of any plain conv network (k_lif_seq_any, ABI 8): opt-in, beside test_sequence ---------------------
     def sequence_any_supported(self):

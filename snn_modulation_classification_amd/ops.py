@@ -112,7 +112,7 @@ def _check_layer_operands(desc, W, b, eps0, eps1, arp, B, tau=None, tau4=None):
 
 def conv_lif_step(desc, x, W, b, alpha, tau_m, alphas, tau_s, eps0, eps1, arp, i2o_W=None, i2o_b=None,
                   out_W=None, out_b=None, want_v=True, out=None, q8=None, stacked=None, finish=None, defer_ro=False,
-                  any_path=False):
+                  any_path=False, w3_path=False):
     """One Conv2dDCLLlayer.forward step (dcll/pytorch_libdcll.py:599-608); state tensors are updated in place.
 
     Returns (s_pooled, p, o, pv_pooled, v) — p / o are None when the corresponding weights are None.
@@ -130,9 +130,14 @@ def conv_lif_step(desc, x, W, b, alpha, tau_m, alphas, tau_s, eps0, eps1, arp, i
     `any_path`: the layer kernel is dcll_conv_lif_step_any — k_lif_step_any, one fp32-MFMA launch with the traces and the pooling
     fused in, for any plain conv layer with c_out <= 32 and a kernel up to 16x16 (step_any_supported) — instead of
     dcll_conv_lif_step's dispatch; the readout tails are the same.  fp32 weights only: with `q8` it raises.
+    `w3_path`: the layer kernel is dcll_conv_lif_step_w3 — k_lif_step_w3, one launch with the traces, the fp32-MFMA chains and the
+    (1,2) pooling fused in, for the (1,3)-kernel / 64-channel layers of radio_ml_conv_ref.yaml (step_w3_supported); the readout
+    tails are the same.  fp32 weights only; combined with `any_path` or `q8` it raises.
     """
     if any_path and q8 is not None:
         raise ValueError("conv_lif_step(any_path=True) reads fp32 weights only (no q8)")
+    if w3_path and (any_path or q8 is not None):
+        raise ValueError("conv_lif_step(w3_path=True) cannot be combined with any_path=True or q8 (fp32 weights, one layer kernel)")
     out = {} if out is None else out
     B = x.shape[0]
     ch, cw, ph, pw = conv_out_shape(desc)
@@ -161,13 +166,14 @@ def conv_lif_step(desc, x, W, b, alpha, tau_m, alphas, tau_s, eps0, eps1, arp, i
     v = buf('v', (B, desc.c_out, ch, cw), want_v)
     p = buf('p', (B, desc.target), i2o_W is not None)
     o = buf('o', (B, desc.target), bool(desc.output_layer))
-    scratch = buf('scratch', (2, B, desc.c_out, ch, cw), pooled and not any_path)
+    scratch = buf('scratch', (2, B, desc.c_out, ch, cw), pooled and not any_path and not w3_path)
     w_scratch = buf('w_scratch', (max(step_any_scratch(desc), 1),), True) if any_path else None       # (not served: the call refuses)
 
     def layer_step(d, *readout_args):
-        """the layer call of this step: dcll_conv_lif_step, or dcll_conv_lif_step_any (w_scratch for scratch, no opts)"""
-        fn = "dcll_conv_lif_step_any" if any_path else "dcll_conv_lif_step"
-        tail = (ptr(w_scratch),) if any_path else (ptr(scratch), opts)
+        """the layer call of this step: dcll_conv_lif_step, dcll_conv_lif_step_any (w_scratch for scratch, no opts) or
+        dcll_conv_lif_step_w3 (neither)"""
+        fn = "dcll_conv_lif_step_w3" if w3_path else "dcll_conv_lif_step_any" if any_path else "dcll_conv_lif_step"
+        tail = () if w3_path else (ptr(w_scratch),) if any_path else (ptr(scratch), opts)
         rc = getattr(_lib.get(), fn)(
             ctypes.byref(d), ptr(x), ptr(W), ptr(b), ptr(alpha), ptr(tau_m), ptr(alphas), ptr(tau_s),
             ptr(eps0), ptr(eps1), ptr(arp), *readout_args, ptr(pv), ptr(v), *tail, B, stream_ptr())
@@ -226,6 +232,28 @@ def step_any_scratch(desc):
     return int(_lib.get().dcll_conv_lif_step_any_scratch(ctypes.byref(desc)))
 
 
+def step_w3_lds(desc):
+    """LDS bytes per workgroup of k_lif_step_w3 (its 8-tile form) on this layer, 0 = not served (dcll_conv_lif_step_w3_lds)."""
+    return int(_lib.get().dcll_conv_lif_step_w3_lds(ctypes.byref(desc)))
+
+
+def step_w3_supported(desc):
+    """True if conv_lif_step(w3_path=True) serves the layer: c_in 1 or 64, c_out 64, kernel (1,3), padding (0,1), pooling (1,2),
+    w a power of two <= 256, h * w % 32 == 0, stride = dilation = groups = 1."""
+    return step_w3_lds(desc) > 0
+
+
+def backward_w3_lds(desc):
+    """LDS bytes per workgroup of the weight-gradient kernel of conv_lif_backward(w3_path=True) on this layer (k_bwd_wgrad_w3;
+    c_in 1: the generic k_bwd_wgrad), 0 = the layer is not served (dcll_conv_lif_backward_w3_lds)."""
+    return int(_lib.get().dcll_conv_lif_backward_w3_lds(ctypes.byref(desc)))
+
+
+def backward_w3_supported(desc):
+    """True if conv_lif_backward(w3_path=True) serves the layer: the layers step_w3_supported names."""
+    return backward_w3_lds(desc) > 0
+
+
 def backward_any_lds(desc):
     """LDS bytes per workgroup of k_bwd_wgrad_any on this layer, 0 = the layer is not served (dcll_conv_lif_backward_any_lds)."""
     return int(_lib.get().dcll_conv_lif_backward_any_lds(ctypes.byref(desc)))
@@ -241,7 +269,7 @@ BWD_ANY_MAX_CHUNKS = 256        # batch chunks (partial rows) of k_bwd_wgrad_any
 
 
 def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want_out, out=None, open_reduce=False, defer=None,
-                      any_path=False):
+                      any_path=False, w3_path=False):
     """Gradients of one layer step (dcll_conv_lif_backward) -> (dW, db, d_outW, d_outb).  `out`: optional dict with
     preallocated 'dW', 'db', 'd_outW', 'd_outb', 'bwd_scratch' (the learning loop writes into the parameters' .grad).
     `open_reduce`: dcll_conv_lif_backward_open — dW / db are NOT written yet; the partial rows of the weight gradient stay
@@ -249,7 +277,11 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
     `defer` (a list; open form): nothing is launched — the prepared call is appended for conv_lif_backward_open_multi.
     `any_path`: dcll_conv_lif_backward_any[_open] — the weight gradient on k_bwd_wgrad_any (fp32 MFMA, any plain conv layer with
     c_out <= 32 and a kernel up to 16x16; backward_any_supported).  With `defer` the single open call is launched at once (there
-    is no multi-layer form of it) and nothing is appended."""
+    is no multi-layer form of it) and nothing is appended.
+    `w3_path`: dcll_conv_lif_backward_w3[_open] — the weight gradient of a 64 -> 64 layer of the (1,3) / (1,2)-pool geometry on
+    k_bwd_wgrad_w3 (fp32 MFMA; backward_w3_supported); `defer` as for `any_path`; combined with `any_path` it raises."""
+    if w3_path and any_path:
+        raise ValueError("conv_lif_backward(w3_path=True) cannot be combined with any_path=True")
     B = eps1.shape[0]
     dev = eps1.device
     out = {} if out is None else out
@@ -275,6 +307,8 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
     nchunk = min(jobs, 1024 if desc.c_in == 1 else 256)      # (first layer: 128-thread workgroups, 6 KB partial rows)
     if any_path:
         nchunk = min(B, BWD_ANY_MAX_CHUNKS)
+    if w3_path and desc.c_in == 64:
+        nchunk = min(-(-B * desc.h * desc.w // 128), BWD_ANY_MAX_CHUNKS)       # (k_bwd_wgrad_w3: one row per 128-pixel block)
     part = nchunk * per_chunk
     if want_out and desc.target <= 32 and K % 32 != 0:
         # the output_ gradient's batch chunks (k_bwd_outgrad_part; K % 32 == 0 runs the MFMA form without them): BEHIND the
@@ -289,8 +323,8 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
     # allocator as soon as ptr() returns, and the NEXT temporary's copy can be given the same block (two expanded stride-0
     # gradients in one call would then alias)
     gp_, go_, gpv_, gv_ = c(g_p), (c(g_o) if want_out else None), c(g_pv), c(g_v)
-    fn = "dcll_conv_lif_backward_any" if any_path else "dcll_conv_lif_backward"
-    if defer is not None and not any_path:       # (open form, launched later with other layers': conv_lif_backward_open_multi)
+    fn = "dcll_conv_lif_backward_w3" if w3_path else "dcll_conv_lif_backward_any" if any_path else "dcll_conv_lif_backward"
+    if defer is not None and not any_path and not w3_path:       # (open form, launched later with other layers': conv_lif_backward_open_multi)
         item = _lib.BwdItem(ctypes.pointer(desc), ptr(eps1), ptr(v), ptr(pv_pooled), ptr(gp_), ptr(go_), ptr(gpv_), ptr(gv_),
                             ptr(i2o_W), ptr(d_outW), ptr(d_outb), ptr(scratch), n_scratch, B, 0, None, 0, 0)
         defer.append(dict(item=item, out=out, desc=desc, dW=dW, db=db, scratch=scratch,

@@ -89,6 +89,17 @@ def parse_args(argv=None):
                         'a kernel up to 16x16) where ConvNetwork.step_any_supported() holds; ignored with a notice elsewhere.  '
                         'The sequence paths are not affected.  Not yet measured against the default path (DESIGN 4.2b; '
                         'experiments/step_any_timing.py)')
+    p.add_argument('--w3_step_path', action='store_true',
+                   help='opt in (radio_ml_conv_ref.yaml: the 64-channel layers with kernel (1,3), padding (0,1), pooling (1,2)): '
+                        'every per-step layer call runs k_lif_step_w3 (traces, fp32-MFMA chains and pooling in one launch) and '
+                        'every learning step takes the weight gradient of the 64 -> 64 layers from k_bwd_wgrad_w3, where '
+                        'ConvNetwork.w3_step_supported() holds; ignored with a notice elsewhere.  The sequence paths are not '
+                        'affected.  Measured on an MI355X, (16,128) plane, five alternating fresh processes, min-max: net.test '
+                        '0.850-0.861 -> 0.490-0.504 ms per timestep at B = 64 (1.7x), 2.839-2.847 -> 1.005-1.013 ms at B = 512 '
+                        '(2.8x); net.learn 19.41-19.51 -> 0.933-0.945 ms at B = 64 (20.5-20.9x), 44.21-44.29 -> 4.151-4.164 ms at '
+                        'B = 512 (10.6-10.7x); the step call of every layer and the backward call of every 64 -> 64 layer are '
+                        'faster, none slower; the weight gradient of the first layer stays on the generic k_bwd_wgrad (1.30 ms of '
+                        'the 4.15 at B = 512).  Table: profiles/r13_w3_learn_timing.txt')
     p.add_argument('--gpus', type=int, default=1, metavar='N',
                    help='ranks (one process per GPU): every batch is sharded over them, the local-learning gradients are '
                         'averaged over the ranks every timestep (one bucketed all-reduce)')
@@ -148,6 +159,7 @@ def main(argv=None):
     net.reset(True)
     _opt_in_any_learning(net, args)
     _opt_in_any_step(net, args)
+    _opt_in_w3_step(net, args)
     parallel.freeze_startup_heap()          # (a full GC pass over the start-up heap costs ~100 ms inside the T-loop)
 
     if not args.no_save:
@@ -313,6 +325,17 @@ def _opt_in_any_step(net, args):
         print('--any_step_path ignored: k_lif_step_any does not serve every layer of this network')
 
 
+def _opt_in_w3_step(net, args):
+    """--w3_step_path: switch the network's per-step layer calls and weight gradients to k_lif_step_w3 / k_bwd_wgrad_w3 where
+    every layer is served."""
+    if not args.w3_step_path:
+        return
+    if net.w3_step_supported():
+        net.w3_step_path = True
+    else:
+        print('--w3_step_path ignored: k_lif_step_w3 / k_bwd_wgrad_w3 do not serve every layer of this network')
+
+
 def main_mnist(args):
     """--data MNIST (reference train.py:118-131): 28x28 images as frozen Poisson spike trains (image2spiketrain,
     gain 100), 10 classes, any conv spec that fits 28x28 (networks/mnist_conv.yaml), per-step protocol for learning
@@ -338,6 +361,7 @@ def main_mnist(args):
     net.reset(True)
     _opt_in_any_learning(net, args)
     _opt_in_any_step(net, args)
+    _opt_in_w3_step(net, args)
     parallel.freeze_startup_heap()          # (a full GC pass over the start-up heap costs ~100 ms inside the T-loop)
     n_test = int(np.ceil(float(args.n_test_samples) / args.batch_size_test))
     if args.synthetic:
