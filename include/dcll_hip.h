@@ -665,6 +665,33 @@ int dcll_conv_lif_backward_w3_open(const dcll_conv_desc *d, const float *eps1, c
                                    float *d_outW, float *d_outb, float *scratch, int64_t scratch_floats, int32_t B,
                                    const float **part, int32_t *nchunk, void *stream);
 
+/*
+ * Found by symbol lookup as well (DCLL_ABI_VERSION stays 10) — dcll_conv_lif_backward_w3 / _w3_open with the weight gradient of the
+ * FIRST layer (c_in 1 -> 64) on k_bwd_wgrad_w3f (csrc/dcll_step_w3.hip) instead of the generic k_bwd_wgrad: a register-only
+ * streaming reduction of the dv plane, 64 x (3 + 1) numbers over B h w pixels.  Arguments, served set (dcll_conv_lif_backward_w3_lds
+ * is the predicate), scratch rule (scratch_floats >= B 64 h w + k x 64 (3 c_in + 1), k >= 1 partial rows; at most 256 are used, at
+ * most one per 128 pixels of the flattened planes for c_in 1), refusals (all before any launch) and B == 0 are those of
+ * dcll_conv_lif_backward_w3[_open]; scratch and eps1 need 4-byte alignment only.
+ * Launch log: "k_bwd_dv", then for c_in 1 "k_bwd_wgrad_w3f" (scratch and eps1 both 16-byte aligned: 16-byte loads) or
+ * "k_bwd_wgrad_w3f (unaligned)" (scalar loads; the same sums, the same bits), for c_in 64 "k_bwd_wgrad_w3" (bit-identical to
+ * dcll_conv_lif_backward_w3), then the reduction / output_ gradient kernels of dcll_conv_lif_backward.  The dv plane left in
+ * scratch[0 : B 64 h w], d_outW and d_outb are dcll_conv_lif_backward_w3's bits.
+ * Sums (c_in 1): chunk c takes the 128-pixel jobs c, c + nchunk, ... of the flattened (B x h w) pixels — its job list i = 0, 1, ...;
+ * the jobs of even and of odd i are two separate sums; inside each, lane q = 0 .. 31 runs the pixels 4 q .. 4 q + 3 of its jobs in
+ * order as one chain per tap (fma) and for the bias (add); the 32 lanes are added by a fixed tree (q ^ 1, q ^ 2, mirror in 8,
+ * mirror in 16, upper 16 + lower 16), then even + odd; the chunks are reduced by k_bwd_reduce[4] / dcll_grad_reduce_adam.  Every
+ * order is fixed: two runs give the same bits, and _open + dcll_grad_reduce_adam gives the closed form's.  dW / db of the first
+ * layer are NOT bit-identical to dcll_conv_lif_backward / dcll_conv_lif_backward_w3 (k_bwd_wgrad): the order differs.
+ */
+int dcll_conv_lif_backward_w3f(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                               const float *g_p, const float *g_o, const float *g_pv, const float *g_v, const float *i2o_W,
+                               float *dW, float *db, float *d_outW, float *d_outb, float *scratch, int64_t scratch_floats,
+                               int32_t B, void *stream);
+int dcll_conv_lif_backward_w3f_open(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                                    const float *g_p, const float *g_o, const float *g_pv, const float *g_v, const float *i2o_W,
+                                    float *d_outW, float *d_outb, float *scratch, int64_t scratch_floats, int32_t B,
+                                    const float **part, int32_t *nchunk, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

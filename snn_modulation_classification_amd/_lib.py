@@ -157,6 +157,8 @@ SIGNATURES = {
     "dcll_conv_lif_backward_w3_lds": (_I64, [_DP]),
     "dcll_conv_lif_backward_w3": (_I32, [_DP] + [_P] * 13 + [_I64, _I32, _P]),
     "dcll_conv_lif_backward_w3_open": (_I32, [_DP] + [_P] * 11 + [_I64, _I32, ctypes.POINTER(ctypes.c_void_p), _IP, _P]),
+    "dcll_conv_lif_backward_w3f": (_I32, [_DP] + [_P] * 13 + [_I64, _I32, _P]),
+    "dcll_conv_lif_backward_w3f_open": (_I32, [_DP] + [_P] * 11 + [_I64, _I32, ctypes.POINTER(ctypes.c_void_p), _IP, _P]),
 }
 
 

@@ -3524,7 +3524,7 @@ __global__ __launch_bounds__(256) void k_bwd_outgrad_mfma(const float *__restric
 }
 
 // the weight-gradient kernel of a backward call: the default dispatch, or one of the opt-in entry points' kernels
-enum wgrad_sel { WGRAD_DEFAULT, WGRAD_ANY, WGRAD_W3 };
+enum wgrad_sel { WGRAD_DEFAULT, WGRAD_ANY, WGRAD_W3, WGRAD_W3F };
 
 // open_part != nullptr: the weight gradient's partial rows are left in scratch (*open_part, *open_nchunk) for
 // dcll_grad_reduce_adam; dW / db are not written
@@ -3537,8 +3537,9 @@ static int conv_lif_backward_impl(const dcll_conv_desc *d, const float *eps1, co
 {
     // WGRAD_ANY: the weight gradient by k_bwd_wgrad_any (dcll_bwd_any.hip) whatever the geometry — none of the specialised
     // kernels, and neither the tap nor the row-width limit of the generic k_bwd_wgrad.  WGRAD_W3: by k_bwd_wgrad_w3
-    // (dcll_step_w3.hip) for the 64 -> 64 layers of the (1,3) geometry; its first layer (c_in 1) keeps the dispatch below
-    const bool any = sel == WGRAD_ANY, w3 = sel == WGRAD_W3;
+    // (dcll_step_w3.hip) for the 64 -> 64 layers of the (1,3) geometry; its first layer (c_in 1) keeps the dispatch below.
+    // WGRAD_W3F: WGRAD_W3 with the first layer on k_bwd_wgrad_w3f (same predicate, scratch rule and refusals)
+    const bool any = sel == WGRAD_ANY, w3f = sel == WGRAD_W3F, w3 = sel == WGRAD_W3 || w3f;
     int rc = check_desc(d);
     if (rc) return rc;
     const bool nopool = d->pool_h == 1 && d->pool_w == 1 && d->target <= 32;
@@ -3565,6 +3566,9 @@ static int conv_lif_backward_impl(const dcll_conv_desc *d, const float *eps1, co
         if (d->c_in == 64) {        // (the launcher's own checks and its LDS reservation, nothing launched)
             long nc = (scratch_floats - nconv) / ((long)d->c_out * ((long)d->c_in * 3 + 1));
             if ((rc = dcll_launch_bwd_wgrad_w3(d, scratch, eps1, scratch + nconv, B, &nc, st, false)) != DCLL_OK) return rc;
+        } else if (w3f) {
+            long nc = (scratch_floats - nconv) / ((long)d->c_out * 4);
+            if ((rc = dcll_launch_bwd_wgrad_w3f(d, scratch, eps1, scratch + nconv, B, &nc, st, false)) != DCLL_OK) return rc;
         }
     }
     const char *dv_form = "k_bwd_dv";        // (the generic kernel: pooling, or more than 32 readout rows)
@@ -3603,6 +3607,8 @@ static int conv_lif_backward_impl(const dcll_conv_desc *d, const float *eps1, co
         if ((rc = dcll_launch_bwd_wgrad_any(d, scratch, eps1, part, B, &nchunk, st)) != DCLL_OK) return rc;
     } else if (w3 && d->c_in == 64) {
         if ((rc = dcll_launch_bwd_wgrad_w3(d, scratch, eps1, part, B, &nchunk, st, true)) != DCLL_OK) return rc;
+    } else if (w3f && d->c_in == 1) {
+        if ((rc = dcll_launch_bwd_wgrad_w3f(d, scratch, eps1, part, B, &nchunk, st, true)) != DCLL_OK) return rc;
     } else if (c32 && d->h == 16 && d->w == 16) {
         if (nchunk > 256) nchunk = 256;
         if (nchunk > B) nchunk = B;
@@ -3765,6 +3771,30 @@ extern "C" int dcll_conv_lif_backward_w3_open(const dcll_conv_desc *d, const flo
     if (!part || !nchunk) return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward_w3_open: null part / nchunk");
     return conv_lif_backward_impl(d, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, nullptr, nullptr, d_outW, d_outb, scratch,
                                   scratch_floats, B, stream, part, nchunk, false, WGRAD_W3);
+}
+
+// found by symbol lookup (the ABI version stays 10): dcll_conv_lif_backward_w3[_open] with the weight gradient of the FIRST layer
+// (c_in 1) on k_bwd_wgrad_w3f (dcll_step_w3.hip) instead of the generic k_bwd_wgrad; a 64 -> 64 layer runs k_bwd_wgrad_w3 and
+// gives dcll_conv_lif_backward_w3's bits.  Served set, scratch rule and refusals are dcll_conv_lif_backward_w3's
+extern "C" int dcll_conv_lif_backward_w3f(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                                          const float *g_p, const float *g_o, const float *g_pv, const float *g_v,
+                                          const float *i2o_W, float *dW, float *db, float *d_outW, float *d_outb,
+                                          float *scratch, int64_t scratch_floats, int32_t B, void *stream)
+{
+    if (B == 0) return DCLL_OK;
+    return conv_lif_backward_impl(d, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, dW, db, d_outW, d_outb, scratch,
+                                  scratch_floats, B, stream, nullptr, nullptr, false, WGRAD_W3F);
+}
+
+extern "C" int dcll_conv_lif_backward_w3f_open(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                                               const float *g_p, const float *g_o, const float *g_pv, const float *g_v,
+                                               const float *i2o_W, float *d_outW, float *d_outb, float *scratch,
+                                               int64_t scratch_floats, int32_t B, const float **part, int32_t *nchunk, void *stream)
+{
+    if (B == 0) return DCLL_OK;
+    if (!part || !nchunk) return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward_w3f_open: null part / nchunk");
+    return conv_lif_backward_impl(d, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, nullptr, nullptr, d_outW, d_outb, scratch,
+                                  scratch_floats, B, stream, part, nchunk, false, WGRAD_W3F);
 }
 
 // dcll_conv_lif_backward_open for n layers — the slices of one learning timestep — with their dv launches as ONE launch

@@ -189,6 +189,12 @@ __attribute__((visibility("hidden")))
 int dcll_launch_bwd_wgrad_w3(const dcll_conv_desc *d, const float *gvf, const float *eps1, float *part, int32_t B,
                              long *nchunk, hipStream_t st, bool launch);
 
+// k_bwd_wgrad_w3f (dcll_step_w3.hip): streaming weight gradient of the first (c_in 1) layer of that geometry; the launcher
+// caps *nchunk and returns it; launch == false: the checks only
+__attribute__((visibility("hidden")))
+int dcll_launch_bwd_wgrad_w3f(const dcll_conv_desc *d, const float *gvf, const float *eps1, float *part, int32_t B,
+                              long *nchunk, hipStream_t st, bool launch);
+
 // dense twins (dcll_dense.hip): one step as an fp32-MFMA GEMM on the updated traces; all T steps with the state on chip
 __attribute__((visibility("hidden")))
 int dcll_launch_dense_mfma(const dcll_dense_desc *d, const float *eps1, const float *W, const float *b, float *arp,

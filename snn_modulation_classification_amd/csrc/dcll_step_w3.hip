@@ -536,3 +536,159 @@ int dcll_launch_bwd_wgrad_w3(const dcll_conv_desc *d, const float *gvf, const fl
     HIP_CHECK_LAUNCH("k_bwd_wgrad_w3");
     return DCLL_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// k_bwd_wgrad_w3f — the weight gradient of the FIRST layer (c_in 1 -> 64) of that geometry
+// (dcll_conv_lif_backward_w3f[_open]; found by symbol lookup, the ABI version stays 10):
+//
+//   dW[co][kx] = sum_{b,p} g[b,co,p] * eps1[b,0,p + kx - 1]  (kx = 0, 1, 2; zero beyond a row's ends),   db[co] = sum g
+//
+// 64 x 3 + 64 numbers reduced over B h w pixels: not matrix work but a streaming reduction of the dv plane g (B 64 h w floats,
+// read once) against the one-channel eps1 plane (B h w floats, cache-resident).  Registers only: nothing is written during the
+// sweep, so a lane reads the +-1 neighbours of its pixels straight from global memory — no LDS image, no row-ownership rule.
+// The flattened pixel stream P = b h w + p (B x H W pixels) is cut into JOBS of WF_PB = 128 consecutive pixels (h w % 32 == 0:
+// a job may span samples and the last one may be short by a multiple of 32; a lane's 4 pixels never leave a row pair, let alone
+// a sample).  chunk = blockIdx.x takes the jobs chunk, chunk + nchunk, chunk + 2 nchunk, ... — the chunk's job list i = 0, 1, ...
+// Wave (cg, jp) = (wave & 3, wave >> 2) of the 512-thread workgroup owns the 16 output channels 16 cg .. 16 cg + 15 and the
+// jobs i = jp, jp + 2, ... of the list; lane (ch, q) = (lane >> 5, lane & 31) owns the channels 16 cg + 8 ch + c, c = 0 .. 7,
+// and the pixels 128 J + 4 q + j, j = 0 .. 3 of every job J of its wave: 8 independent 16-byte loads of g per lane and job.
+// SUMMATION ORDER of one output (co, column) of chunk k — restated on the CPU by tests/bwd_w3f_cases.py:
+//   1. lane (q), wave jp: four accumulators a0, a1, a2 (taps) and ab (bias) start at 0 and take the wave's jobs in increasing i
+//      and inside a job the pixels j = 0, 1, 2, 3 in order: a0 = fma(g, eL, a0), a1 = fma(g, eC, a1), a2 = fma(g, eR, a2),
+//      ab = ab + g, with eL / eR = the left / right neighbour in the row, 0 at x = 0 / x = w - 1;
+//   2. the 32 lanes q of a half wave by the fixed DPP tree (half_sum_to_lane31: v += v[q ^ 1]; v += v[q ^ 2]; v += mirror in
+//      the group of 8; v += mirror in the row of 16; row 1 += row 0);
+//   3. the two waves of a channel group through LDS: total(jp 0) + total(jp 1).
+// Partial rows: part[chunk][co][4] = (kx 0, kx 1, kx 2, bias): the rowlen-4 format k_bwd_reduce[4] and dcll_grad_reduce_adam
+// consume; at most WF_MAX_CHUNKS = 256 chunks and at most one per job.  Every sum has a fixed order: two runs give the same
+// bits, and the open form + the fused reduction gives the closed form's bits.  NOT bit-identical to k_bwd_wgrad (the default
+// path and dcll_conv_lif_backward_w3 on this layer): the summation order differs.
+// Two forms with the SAME order, hence the same bits: 16-byte loads of g and eps1 where both pointers are 16-byte aligned
+// (h w % 4 == 0 keeps every lane's 4 pixels aligned then), scalar loads otherwise (the ABI asks for 4-byte alignment only).
+constexpr int WF_THREADS = 512, WF_PB = 128, WF_MAX_CHUNKS = 256;
+
+// sum over each 32-lane half of the wave; valid in lanes 31 and 63 (wave_sum_to_lane63 without its last step)
+__device__ __forceinline__ float half_sum_to_lane31(float v)
+{
+    v = dpp_add<0xB1, 0xF>(v);       // quad_perm [1,0,3,2]
+    v = dpp_add<0x4E, 0xF>(v);       // quad_perm [2,3,0,1]
+    v = dpp_add<0x141, 0xF>(v);      // row_half_mirror
+    v = dpp_add<0x140, 0xF>(v);      // row_mirror      -> every lane holds its 16-lane row sum
+    v = dpp_add<0x142, 0xA>(v);      // row_bcast15     -> rows 1,3 += previous row
+    return v;
+}
+
+template <bool ALIGNED>
+__device__ __forceinline__ void wf_load4(const float *__restrict__ p, float (&r)[4])
+{
+    if constexpr (ALIGNED) {
+        const f32x4 t = *(const f32x4 *)p;
+        r[0] = t[0], r[1] = t[1], r[2] = t[2], r[3] = t[3];
+    } else {
+        r[0] = p[0], r[1] = p[1], r[2] = p[2], r[3] = p[3];
+    }
+}
+
+template <bool ALIGNED>
+__global__ __launch_bounds__(WF_THREADS) void k_bwd_wgrad_w3f(const float *__restrict__ gvf, const float *__restrict__ eps1,
+                                                             float *__restrict__ part, int ntot, int HW, int w)
+{
+    __shared__ float red[4 * 16 * 4];                   // the totals of the waves jp = 1: [cg][channel of the group][column]
+    const int tid = threadIdx.x, lane = tid & 63, ch = lane >> 5, q = lane & 31;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int cg = wv & 3, jp = wv >> 2;
+    const int NTS = HW >> 5;                            // 32-pixel tiles per sample
+    const int njob = (ntot + 3) >> 2;                   // 4 tiles per job; ntot = B NTS < 2^31 - 8 (the launcher)
+    const int c0 = 16 * cg + 8 * ch;
+    float a0[8], a1[8], a2[8], ab[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) a0[c] = a1[c] = a2[c] = ab[c] = 0.0f;
+
+    for (long J = (long)blockIdx.x + (long)jp * gridDim.x; J < njob; J += 2L * gridDim.x) {
+        const int G = (int)J * 4 + (q >> 3);            // the 32-pixel tile of this lane's 4 pixels
+        if (G >= ntot) continue;                        // (the short last job)
+        const int b = G / NTS, ps = (G - b * NTS) * 32 + 4 * (q & 7);   // sample, first of the 4 pixels in it
+        const float *ep = eps1 + (long)b * HW + ps;
+        const float *gp = gvf + ((long)b * 64 + c0) * HW + ps;
+        float g[8][4], e[6];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) wf_load4<ALIGNED>(gp + (long)c * HW, g[c]);
+        {
+            float ec[4];
+            wf_load4<ALIGNED>(ep, ec);
+            e[1] = ec[0], e[2] = ec[1], e[3] = ec[2], e[4] = ec[3];
+        }
+        // the neighbours outside the 4 pixels: read only where they lie in the row (then in the sample); w >= 4: the 4 pixels
+        // are in one row; w = 2: two rows, the masks below cut every neighbour
+        const int x0 = ps & (w - 1);
+        e[0] = x0 != 0 ? ep[-1] : 0.0f;
+        e[5] = ((x0 + 3) & (w - 1)) != w - 1 ? ep[4] : 0.0f;
+        float eL[4], eR[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int x = (x0 + j) & (w - 1);
+            eL[j] = x != 0 ? e[j] : 0.0f;
+            eR[j] = x != w - 1 ? e[j + 2] : 0.0f;
+        }
+#pragma unroll
+        for (int c = 0; c < 8; ++c)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                a0[c] = __builtin_fmaf(g[c][j], eL[j], a0[c]);
+                a1[c] = __builtin_fmaf(g[c][j], e[j + 1], a1[c]);
+                a2[c] = __builtin_fmaf(g[c][j], eR[j], a2[c]);
+                ab[c] = ab[c] + g[c][j];
+            }
+    }
+    // ---- the 32 lanes of a half wave (fixed tree), then the two waves of the channel group: jp 0 + jp 1
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        a0[c] = half_sum_to_lane31(a0[c]);
+        a1[c] = half_sum_to_lane31(a1[c]);
+        a2[c] = half_sum_to_lane31(a2[c]);
+        ab[c] = half_sum_to_lane31(ab[c]);
+    }
+    float *rr = red + (cg * 16 + 8 * ch) * 4;
+    if (jp == 1 && q == 31) {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) rr[4 * c] = a0[c], rr[4 * c + 1] = a1[c], rr[4 * c + 2] = a2[c], rr[4 * c + 3] = ab[c];
+    }
+    __syncthreads();
+    if (jp == 0 && q == 31) {
+        float *prow = part + ((long)blockIdx.x * 64 + c0) * 4;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            prow[4 * c] = a0[c] + rr[4 * c];
+            prow[4 * c + 1] = a1[c] + rr[4 * c + 1];
+            prow[4 * c + 2] = a2[c] + rr[4 * c + 2];
+            prow[4 * c + 3] = ab[c] + rr[4 * c + 3];
+        }
+    }
+}
+
+// gvf: the dv plane (B, 64, h, w); part: room for *nchunk partial rows of 64 x 4 floats on entry, the number written on
+// return.  launch == false: the checks only (conv_lif_backward_impl calls this form before its first launch)
+int dcll_launch_bwd_wgrad_w3f(const dcll_conv_desc *d, const float *gvf, const float *eps1, float *part, int32_t B, long *nchunk,
+                              hipStream_t st, bool launch)
+{
+    const char *who = "dcll_conv_lif_backward_w3f";
+    const long ntot = (long)B * ((long)d->h * d->w / 32);
+    if (ntot > 0x7fffffffL - 8) return fail(DCLL_ERR_INVALID, "batch x tiles exceeds the grid limit", who);
+    long nc = *nchunk;
+    const long njob = (ntot + WF_PB / 32 - 1) / (WF_PB / 32);
+    if (nc > WF_MAX_CHUNKS) nc = WF_MAX_CHUNKS;
+    if (nc > njob) nc = njob;
+    if (d->c_in != 1 || d->c_out != 64 || ((long)d->h * d->w) % 32 != 0 || d->w < 2 || (d->w & (d->w - 1)) != 0 || nc < 1)
+        return fail(DCLL_ERR_LAUNCH, "k_bwd_wgrad_w3f: launch layout outside the predicate's", who);
+    *nchunk = nc;
+    if (!launch) return DCLL_OK;
+    const bool aligned = (((uintptr_t)gvf | (uintptr_t)eps1) & 15) == 0;
+    if (aligned)
+        hipLaunchKernelGGL(k_bwd_wgrad_w3f<true>, dim3((unsigned)nc), dim3(WF_THREADS), 0, st, gvf, eps1, part, (int)ntot,
+                           d->h * d->w, d->w);
+    else
+        hipLaunchKernelGGL(k_bwd_wgrad_w3f<false>, dim3((unsigned)nc), dim3(WF_THREADS), 0, st, gvf, eps1, part, (int)ntot,
+                           d->h * d->w, d->w);
+    HIP_CHECK_LAUNCH(aligned ? "k_bwd_wgrad_w3f" : "k_bwd_wgrad_w3f (unaligned)");
+    return DCLL_OK;
+}

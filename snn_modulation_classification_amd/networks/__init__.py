@@ -307,7 +307,7 @@ class ConvNetwork(torch.nn.Module):
             walk(s.__dict__.get('_learn_bufs', {}))
             sig.append(bool(s.any_learning_path))
             sig.append(bool(L.i2h.any_step_path))
-            sig.append((bool(s.w3_learning_path), bool(L.i2h.w3_step_path)))
+            sig.append((bool(s.w3_learning_path), bool(L.i2h.w3_step_path), bool(s.w3_first_wgrad)))
             for t in s._adam_tensors(advance=False):
                 sig += [t['param'].data_ptr(), t['grad'].data_ptr(), t['exp_avg'].data_ptr(),
                         t['exp_avg_sq'].data_ptr(), t['weight_decay'], t['beta1'], t['beta2'], t['eps']]
@@ -940,6 +940,25 @@ class ConvNetwork(torch.nn.Module):
         for s in self.dcll_slices:              # (part of _graph_signature and _test_signature: a capture of the other path is retaken)
             s.w3_learning_path = on
             s.dclllayer.i2h.w3_step_path = on
+            if not on:
+                s.w3_first_wgrad = False        # (it rides on the w3 path)
+
+    @property
+    def w3_first_wgrad(self):
+        """True: with w3_step_path, the first layer (c_in 1 -> 64) takes its weight gradient from k_bwd_wgrad_w3f (a register-only
+        streaming reduction of the dv plane; dcll_conv_lif_backward_w3f[_open]) instead of the generic k_bwd_wgrad; the 64 -> 64
+        layers and everything else are w3_step_path's.  That layer's dW / db are then summed in another order (not bit-identical,
+        inside the weight-gradient tolerance).  Default False; setting it True while w3_step_path is off raises DCLLUnsupported
+        and leaves it off; w3_step_path = False clears it; switching it off is always allowed."""
+        return all(s.w3_first_wgrad for s in self.dcll_slices)
+
+    @w3_first_wgrad.setter
+    def w3_first_wgrad(self, on):
+        on = bool(on)
+        if on and not self.w3_step_path:
+            raise ops._lib.DCLLUnsupported('w3_first_wgrad needs w3_step_path (set it first)')
+        for s in self.dcll_slices:              # (part of _graph_signature: a captured timestep of the other path is retaken)
+            s.w3_first_wgrad = on
 
     # -- the fused path of any plain conv network (k_lif_seq_any, ABI 8): opt-in, beside test_sequence ---------------------
     def sequence_any_supported(self):

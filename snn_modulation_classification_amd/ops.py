@@ -266,10 +266,11 @@ def backward_any_supported(desc):
 
 
 BWD_ANY_MAX_CHUNKS = 256        # batch chunks (partial rows) of k_bwd_wgrad_any, at most
+BWD_W3F_PB = 128                # pixels of a job of k_bwd_wgrad_w3f (the flattened B x h w stream): at most one partial row per job
 
 
 def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want_out, out=None, open_reduce=False, defer=None,
-                      any_path=False, w3_path=False):
+                      any_path=False, w3_path=False, w3_first=False):
     """Gradients of one layer step (dcll_conv_lif_backward) -> (dW, db, d_outW, d_outb).  `out`: optional dict with
     preallocated 'dW', 'db', 'd_outW', 'd_outb', 'bwd_scratch' (the learning loop writes into the parameters' .grad).
     `open_reduce`: dcll_conv_lif_backward_open — dW / db are NOT written yet; the partial rows of the weight gradient stay
@@ -279,9 +280,13 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
     c_out <= 32 and a kernel up to 16x16; backward_any_supported).  With `defer` the single open call is launched at once (there
     is no multi-layer form of it) and nothing is appended.
     `w3_path`: dcll_conv_lif_backward_w3[_open] — the weight gradient of a 64 -> 64 layer of the (1,3) / (1,2)-pool geometry on
-    k_bwd_wgrad_w3 (fp32 MFMA; backward_w3_supported); `defer` as for `any_path`; combined with `any_path` it raises."""
+    k_bwd_wgrad_w3 (fp32 MFMA; backward_w3_supported); `defer` as for `any_path`; combined with `any_path` it raises.
+    `w3_first` (with `w3_path`; alone it raises): dcll_conv_lif_backward_w3f[_open] — the same, and the first layer of that geometry
+    (c_in 1) takes its weight gradient from k_bwd_wgrad_w3f (a streaming reduction) instead of the generic k_bwd_wgrad."""
     if w3_path and any_path:
         raise ValueError("conv_lif_backward(w3_path=True) cannot be combined with any_path=True")
+    if w3_first and not w3_path:
+        raise ValueError("conv_lif_backward(w3_first=True) needs w3_path=True")
     B = eps1.shape[0]
     dev = eps1.device
     out = {} if out is None else out
@@ -309,6 +314,8 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
         nchunk = min(B, BWD_ANY_MAX_CHUNKS)
     if w3_path and desc.c_in == 64:
         nchunk = min(-(-B * desc.h * desc.w // 128), BWD_ANY_MAX_CHUNKS)       # (k_bwd_wgrad_w3: one row per 128-pixel block)
+    if w3_first and desc.c_in == 1:
+        nchunk = min(-(-B * desc.h * desc.w // BWD_W3F_PB), BWD_ANY_MAX_CHUNKS)  # (k_bwd_wgrad_w3f: one row per job)
     part = nchunk * per_chunk
     if want_out and desc.target <= 32 and K % 32 != 0:
         # the output_ gradient's batch chunks (k_bwd_outgrad_part; K % 32 == 0 runs the MFMA form without them): BEHIND the
@@ -323,7 +330,7 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
     # allocator as soon as ptr() returns, and the NEXT temporary's copy can be given the same block (two expanded stride-0
     # gradients in one call would then alias)
     gp_, go_, gpv_, gv_ = c(g_p), (c(g_o) if want_out else None), c(g_pv), c(g_v)
-    fn = "dcll_conv_lif_backward_w3" if w3_path else "dcll_conv_lif_backward_any" if any_path else "dcll_conv_lif_backward"
+    fn = "dcll_conv_lif_backward_w3f" if w3_first else "dcll_conv_lif_backward_w3" if w3_path else "dcll_conv_lif_backward_any" if any_path else "dcll_conv_lif_backward"
     if defer is not None and not any_path and not w3_path:       # (open form, launched later with other layers': conv_lif_backward_open_multi)
         item = _lib.BwdItem(ctypes.pointer(desc), ptr(eps1), ptr(v), ptr(pv_pooled), ptr(gp_), ptr(go_), ptr(gpv_), ptr(gv_),
                             ptr(i2o_W), ptr(d_outW), ptr(d_outb), ptr(scratch), n_scratch, B, 0, None, 0, 0)

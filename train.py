@@ -98,8 +98,16 @@ def parse_args(argv=None):
                         '0.850-0.861 -> 0.490-0.504 ms per timestep at B = 64 (1.7x), 2.839-2.847 -> 1.005-1.013 ms at B = 512 '
                         '(2.8x); net.learn 19.41-19.51 -> 0.933-0.945 ms at B = 64 (20.5-20.9x), 44.21-44.29 -> 4.151-4.164 ms at '
                         'B = 512 (10.6-10.7x); the step call of every layer and the backward call of every 64 -> 64 layer are '
-                        'faster, none slower; the weight gradient of the first layer stays on the generic k_bwd_wgrad (1.30 ms of '
-                        'the 4.15 at B = 512).  Table: profiles/r13_w3_learn_timing.txt')
+                        'faster, none slower; the first layer\'s open backward call is 1.30 ms of the 4.15 at B = 512, of which the '
+                        'generic k_bwd_wgrad is 0.48 ms: see --w3_first_wgrad.  Table: profiles/r13_w3_learn_timing.txt')
+    p.add_argument('--w3_first_wgrad', action='store_true',
+                   help='opt in, effective only together with --w3_step_path on a network it serves: the first layer (c_in 1 -> '
+                        '64) takes its weight gradient from k_bwd_wgrad_w3f (a register-only streaming reduction of the dv plane) '
+                        'instead of the generic k_bwd_wgrad; ignored with a notice elsewhere.  Measured on an MI355X, (16,128) plane, '
+                        'five alternating fresh processes, min-max: that kernel 479.6 -> 52.2 us at B = 512 (0.83 of the copy rate), '
+                        'layer 0\'s open backward call 1294.6-1298.8 -> 865.1-867.9 us, net.learn 4.083-4.110 -> 3.665-3.688 ms '
+                        '(1.11-1.12x); at B = 64 the call 176.6-179.9 -> 102.9-104.9 us, net.learn 1.116-1.185 -> 1.034-1.442 ms: '
+                        'ranges overlap, not claimed faster.  Table: profiles/r14_w3f_wgrad_timing.txt')
     p.add_argument('--gpus', type=int, default=1, metavar='N',
                    help='ranks (one process per GPU): every batch is sharded over them, the local-learning gradients are '
                         'averaged over the ranks every timestep (one bucketed all-reduce)')
@@ -327,13 +335,20 @@ def _opt_in_any_step(net, args):
 
 def _opt_in_w3_step(net, args):
     """--w3_step_path: switch the network's per-step layer calls and weight gradients to k_lif_step_w3 / k_bwd_wgrad_w3 where
-    every layer is served."""
+    every layer is served; --w3_first_wgrad with it: the first layer's weight gradient on k_bwd_wgrad_w3f."""
+    first = getattr(args, 'w3_first_wgrad', False)
     if not args.w3_step_path:
+        if first:
+            print('--w3_first_wgrad ignored: it rides on --w3_step_path, which is not given')
         return
     if net.w3_step_supported():
         net.w3_step_path = True
+        if first:
+            net.w3_first_wgrad = True
     else:
         print('--w3_step_path ignored: k_lif_step_w3 / k_bwd_wgrad_w3 do not serve every layer of this network')
+        if first:
+            print('--w3_first_wgrad ignored: --w3_step_path is not in effect on this network')
 
 
 def main_mnist(args):
