@@ -692,6 +692,32 @@ int dcll_conv_lif_backward_w3f_open(const dcll_conv_desc *d, const float *eps1, 
                                     float *d_outW, float *d_outb, float *scratch, int64_t scratch_floats, int32_t B,
                                     const float **part, int32_t *nchunk, void *stream);
 
+/*
+ * Found by symbol lookup as well (DCLL_ABI_VERSION stays 10) — dcll_conv_lif_backward_w3 / _w3_open with a flag word in front of
+ * the stream.  flags == 0: dcll_conv_lif_backward_w3[_open], bits and launch log; DCLL_W3_FIRST_WGRAD: those of
+ * dcll_conv_lif_backward_w3f[_open].  DCLL_W3_DV: the "k_bwd_dv" launch of either is replaced by k_bwd_dv_w3
+ * (csrc/dcll_step_w3.hip), a streaming form of the same formula for these layers' (1,2) pooling: a thread owns two consecutive
+ * pooled positions (four un-pooled elements: 16-byte loads and stores) with their readout weights in registers over a chunk of
+ * samples.  The dv plane left in scratch[0 : B 64 h w] is k_bwd_dv's BIT FOR BIT (same operations in the same order; a tie of the
+ * two sigmoids of a pair goes to the left element), so the weight gradient, the reduction, d_outW and d_outb behind it are the
+ * bits of the same call without the flag.  Served set, scratch rule and refusals (all before any launch) are
+ * dcll_conv_lif_backward_w3's; any other flag bit: DCLL_ERR_INVALID; B == 0 (with valid flags): DCLL_OK, nothing else is looked at.
+ * target > 32 keeps k_bwd_dv.  g_p, g_pv and g_v may each be NULL.
+ * Launch log with DCLL_W3_DV: "k_bwd_dv_w3" (v, scratch and g_v 16-byte and g_pv and i2o_W 8-byte aligned) or "k_bwd_dv_w3
+ * (unaligned)" (scalar loads, the same bits; the ABI asks for 4-byte alignment only) or, for target > 32, "k_bwd_dv"; then as
+ * without the flag.
+ */
+#define DCLL_W3_FIRST_WGRAD 1u
+#define DCLL_W3_DV 2u
+int dcll_conv_lif_backward_w3_ex(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                                 const float *g_p, const float *g_o, const float *g_pv, const float *g_v, const float *i2o_W,
+                                 float *dW, float *db, float *d_outW, float *d_outb, float *scratch, int64_t scratch_floats,
+                                 int32_t B, uint32_t flags, void *stream);
+int dcll_conv_lif_backward_w3_ex_open(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                                      const float *g_p, const float *g_o, const float *g_pv, const float *g_v, const float *i2o_W,
+                                      float *d_outW, float *d_outb, float *scratch, int64_t scratch_floats, int32_t B,
+                                      const float **part, int32_t *nchunk, uint32_t flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

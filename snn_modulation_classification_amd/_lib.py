@@ -159,6 +159,9 @@ SIGNATURES = {
     "dcll_conv_lif_backward_w3_open": (_I32, [_DP] + [_P] * 11 + [_I64, _I32, ctypes.POINTER(ctypes.c_void_p), _IP, _P]),
     "dcll_conv_lif_backward_w3f": (_I32, [_DP] + [_P] * 13 + [_I64, _I32, _P]),
     "dcll_conv_lif_backward_w3f_open": (_I32, [_DP] + [_P] * 11 + [_I64, _I32, ctypes.POINTER(ctypes.c_void_p), _IP, _P]),
+    "dcll_conv_lif_backward_w3_ex": (_I32, [_DP] + [_P] * 13 + [_I64, _I32, ctypes.c_uint32, _P]),
+    "dcll_conv_lif_backward_w3_ex_open": (_I32, [_DP] + [_P] * 11 + [_I64, _I32, ctypes.POINTER(ctypes.c_void_p), _IP,
+                                                 ctypes.c_uint32, _P]),
 }
 
 

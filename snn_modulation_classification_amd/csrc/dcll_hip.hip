@@ -3533,12 +3533,13 @@ static int conv_lif_backward_impl(const dcll_conv_desc *d, const float *eps1, co
                                   const float *i2o_W, float *dW, float *db, float *d_outW, float *d_outb,
                                   float *scratch, int64_t scratch_floats, int32_t B, void *stream,
                                   const float **open_part, int32_t *open_nchunk, bool dv_done = false,
-                                  wgrad_sel sel = WGRAD_DEFAULT)
+                                  wgrad_sel sel = WGRAD_DEFAULT, bool dv_w3 = false)
 {
     // WGRAD_ANY: the weight gradient by k_bwd_wgrad_any (dcll_bwd_any.hip) whatever the geometry — none of the specialised
     // kernels, and neither the tap nor the row-width limit of the generic k_bwd_wgrad.  WGRAD_W3: by k_bwd_wgrad_w3
     // (dcll_step_w3.hip) for the 64 -> 64 layers of the (1,3) geometry; its first layer (c_in 1) keeps the dispatch below.
     // WGRAD_W3F: WGRAD_W3 with the first layer on k_bwd_wgrad_w3f (same predicate, scratch rule and refusals)
+    // dv_w3 (with WGRAD_W3 / WGRAD_W3F only): the dv plane by k_bwd_dv_w3 (dcll_step_w3.hip) instead of k_bwd_dv, same bits
     const bool any = sel == WGRAD_ANY, w3f = sel == WGRAD_W3F, w3 = sel == WGRAD_W3 || w3f;
     int rc = check_desc(d);
     if (rc) return rc;
@@ -3592,8 +3593,12 @@ static int conv_lif_backward_impl(const dcll_conv_desc *d, const float *eps1, co
         else { DCLL_DV(32); dv_form = v ? "k_bwd_dv_nopool<32>" : "k_bwd_dv_nopool<32> (from pv)"; }
 #undef DCLL_DV
     } else {
-        hipLaunchKernelGGL(k_bwd_dv, dim3(nblk(nconv, 256)), dim3(256), 0, st, *d, ch, cw, ph, pw, v, g_p, g_pv, g_v, i2o_W,
-                           scratch, nconv);
+        const char *form = nullptr;
+        if (dv_w3 && w3 && (rc = dcll_launch_bwd_dv_w3(d, v, g_p, g_pv, g_v, i2o_W, scratch, B, st, &form)) != DCLL_OK) return rc;
+        if (form) dv_form = form;
+        else        // (without dv_w3, or a layer k_bwd_dv_w3 leaves to the generic kernel: more than 32 readout rows)
+            hipLaunchKernelGGL(k_bwd_dv, dim3(nblk(nconv, 256)), dim3(256), 0, st, *d, ch, cw, ph, pw, v, g_p, g_pv, g_v, i2o_W,
+                               scratch, nconv);
     }
     if (!dv_done) HIP_CHECK_LAUNCH(dv_form);
     // weight gradient: partial sums over batch chunks (after the g_v_full plane in scratch), then a fixed-order reduce
@@ -3795,6 +3800,36 @@ extern "C" int dcll_conv_lif_backward_w3f_open(const dcll_conv_desc *d, const fl
     if (!part || !nchunk) return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward_w3f_open: null part / nchunk");
     return conv_lif_backward_impl(d, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, nullptr, nullptr, d_outW, d_outb, scratch,
                                   scratch_floats, B, stream, part, nchunk, false, WGRAD_W3F);
+}
+
+// found by symbol lookup (the ABI version stays 10): dcll_conv_lif_backward_w3[_open] with a flag word.  flags == 0 is
+// dcll_conv_lif_backward_w3, DCLL_W3_FIRST_WGRAD dcll_conv_lif_backward_w3f (same bits, same launch log); DCLL_W3_DV replaces the
+// k_bwd_dv launch of either by k_bwd_dv_w3 (dcll_step_w3.hip; bit-identical dv plane, so everything behind it is unchanged too;
+// target > 32 keeps k_bwd_dv).  Any other bit: DCLL_ERR_INVALID, before B is looked at
+extern "C" int dcll_conv_lif_backward_w3_ex(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                                            const float *g_p, const float *g_o, const float *g_pv, const float *g_v,
+                                            const float *i2o_W, float *dW, float *db, float *d_outW, float *d_outb,
+                                            float *scratch, int64_t scratch_floats, int32_t B, uint32_t flags, void *stream)
+{
+    if (flags & ~(uint32_t)(DCLL_W3_FIRST_WGRAD | DCLL_W3_DV)) return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward_w3_ex: unknown flag bits");
+    if (B == 0) return DCLL_OK;
+    return conv_lif_backward_impl(d, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, dW, db, d_outW, d_outb, scratch,
+                                  scratch_floats, B, stream, nullptr, nullptr, false,
+                                  (flags & DCLL_W3_FIRST_WGRAD) ? WGRAD_W3F : WGRAD_W3, (flags & DCLL_W3_DV) != 0);
+}
+
+extern "C" int dcll_conv_lif_backward_w3_ex_open(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                                                 const float *g_p, const float *g_o, const float *g_pv, const float *g_v,
+                                                 const float *i2o_W, float *d_outW, float *d_outb, float *scratch,
+                                                 int64_t scratch_floats, int32_t B, const float **part, int32_t *nchunk,
+                                                 uint32_t flags, void *stream)
+{
+    if (flags & ~(uint32_t)(DCLL_W3_FIRST_WGRAD | DCLL_W3_DV)) return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward_w3_ex_open: unknown flag bits");
+    if (B == 0) return DCLL_OK;
+    if (!part || !nchunk) return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward_w3_ex_open: null part / nchunk");
+    return conv_lif_backward_impl(d, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, nullptr, nullptr, d_outW, d_outb, scratch,
+                                  scratch_floats, B, stream, part, nchunk, false,
+                                  (flags & DCLL_W3_FIRST_WGRAD) ? WGRAD_W3F : WGRAD_W3, (flags & DCLL_W3_DV) != 0);
 }
 
 // dcll_conv_lif_backward_open for n layers — the slices of one learning timestep — with their dv launches as ONE launch

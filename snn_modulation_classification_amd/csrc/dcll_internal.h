@@ -195,6 +195,12 @@ __attribute__((visibility("hidden")))
 int dcll_launch_bwd_wgrad_w3f(const dcll_conv_desc *d, const float *gvf, const float *eps1, float *part, int32_t B,
                               long *nchunk, hipStream_t st, bool launch);
 
+// k_bwd_dv_w3 (dcll_step_w3.hip): the dv plane of a layer of that geometry, a streaming form of k_bwd_dv for its (1,2) pooling.
+// Launches and sets *form to the kernel's name for the launch log; *form == nullptr: not served (target > 32), nothing launched
+__attribute__((visibility("hidden")))
+int dcll_launch_bwd_dv_w3(const dcll_conv_desc *d, const float *v, const float *g_p, const float *g_pv, const float *g_v,
+                          const float *i2o_W, float *gvf, int32_t B, hipStream_t st, const char **form);
+
 // dense twins (dcll_dense.hip): one step as an fp32-MFMA GEMM on the updated traces; all T steps with the state on chip
 __attribute__((visibility("hidden")))
 int dcll_launch_dense_mfma(const dcll_dense_desc *d, const float *eps1, const float *W, const float *b, float *arp,

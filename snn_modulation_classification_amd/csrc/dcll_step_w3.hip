@@ -692,3 +692,143 @@ int dcll_launch_bwd_wgrad_w3f(const dcll_conv_desc *d, const float *gvf, const f
     HIP_CHECK_LAUNCH(aligned ? "k_bwd_wgrad_w3f" : "k_bwd_wgrad_w3f (unaligned)");
     return DCLL_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// k_bwd_dv_w3 — the dv plane of a layer of that geometry (dcll_conv_lif_backward_w3_ex[_open] with DCLL_W3_DV; found by symbol
+// lookup, the ABI version stays 10): k_bwd_dv (dcll_hip.hip) for pooling (1,2) on an even width, where the geometry is flat —
+// pooled position k of a sample's K = 64 h w / 2 is the un-pooled pair 2k, 2k + 1 of its 2K elements, K % 1024 == 0 (h w % 32
+// == 0): no tail in k, only the batch is ragged.  A thread owns TWO consecutive pooled positions — one 16-byte load of v (and of
+// g_v), one 16-byte store of dv, 8-byte loads of g_pv and of every i2o_W row — with its NP x 2 readout weights in registers
+// (NP = target rounded up to 8; bwd_dv_nopool_body's trick) over a chunk of DW_PB samples, whose g_p rows go through LDS and
+// come back as broadcasts; the loads of DW_G samples are issued before the first is used.  Workgroup = 512 pooled positions x
+// one batch chunk; grid (K / 512, ceil(B / DW_PB)).
+// ARITHMETIC = k_bwd_dv's, bit for bit (-ffp-contract=off; tests/dv_w3_cases.py restates it): pv = sigmoidf_dev(v) of both
+// elements; element 0 wins unless pv1 > pv0 (the comparison is on the sigmoids: a first-maximum tie goes to element 0); the
+// winner's g = (g_pv or 0) + acc, acc = 0, acc = fmaf(g_p[b][n], i2o_W[n][k], acc), n = 0 .. target - 1 in that order (no sum
+// without g_p), the loser's g = 0; out = g * pv * (1 - pv), + g_v where given.  The padding terms n >= target are
+// fmaf(-0, +0, acc): the product is -0, and x + (-0) == x for EVERY x, -0 included (a +0 product would turn an acc of -0 —
+// reachable by underflow — into +0).
+// Two forms with the same bits: the vector loads above where v, dv and g_v are 16-byte and g_pv and i2o_W 8-byte aligned (K is
+// even: every row then is), scalar loads otherwise — the ABI asks for 4-byte alignment only.
+#ifndef DW_PER_BLOCK            // samples per workgroup (experiments/build_variant.sh -DDW_PER_BLOCK=..: the sweep in
+#define DW_PER_BLOCK 8          // profiles/r15_w3_dv_timing.txt); restated by tests/dv_w3_cases.py
+#endif
+constexpr int DW_THREADS = 256, DW_POS = 2 * DW_THREADS, DW_PB = DW_PER_BLOCK, DW_G = 4;
+
+template <bool ALIGNED>
+__device__ __forceinline__ void dw_load2(const float *__restrict__ p, float (&r)[2])
+{
+    if constexpr (ALIGNED) {
+        const f32x2 t = *(const f32x2 *)p;
+        r[0] = t[0], r[1] = t[1];
+    } else {
+        r[0] = p[0], r[1] = p[1];
+    }
+}
+
+template <int NP, bool ALIGNED>
+__global__ __launch_bounds__(DW_THREADS, NP <= 24 ? 4 : 3) void k_bwd_dv_w3(const int K, const int N, const float *__restrict__ v,
+                                                         const float *__restrict__ g_p, const float *__restrict__ g_pv,
+                                                         const float *__restrict__ g_v, const float *__restrict__ i2o_W,
+                                                         float *__restrict__ gvf, const int B)
+{
+    __shared__ __attribute__((aligned(16))) float gp[DW_PB][32];
+    const int b0 = (int)blockIdx.y * DW_PB, b1 = min(B, b0 + DW_PB);
+    for (int e = threadIdx.x; e < DW_PB * 32; e += DW_THREADS) {
+        const int bb = b0 + (e >> 5), n = e & 31;
+        gp[e >> 5][n] = (g_p && n < N && bb < b1) ? g_p[(long)bb * N + n] : -0.0f;
+    }
+    __syncthreads();
+    const int k = (int)blockIdx.x * DW_POS + 2 * threadIdx.x;          // (K % DW_POS == 0: every thread has its two positions)
+    float wk[NP][2];
+#pragma unroll
+    for (int n = 0; n < NP; ++n) {
+        wk[n][0] = wk[n][1] = 0.0f;
+        if (g_p && n < N) dw_load2<ALIGNED>(i2o_W + (long)n * K + k, wk[n]);
+    }
+    for (int bg = b0; bg < b1; bg += DW_G) {
+        float vv[DW_G][4], gg[DW_G][2], ga[DW_G][4];
+#pragma unroll
+        for (int q = 0; q < DW_G; ++q) {
+            const int b = min(bg + q, b1 - 1);
+            const long ip = (long)b * K + k;
+            wf_load4<ALIGNED>(v + 2 * ip, vv[q]);
+            gg[q][0] = gg[q][1] = 0.0f;
+            if (g_pv) dw_load2<ALIGNED>(g_pv + ip, gg[q]);
+            ga[q][0] = ga[q][1] = ga[q][2] = ga[q][3] = 0.0f;
+            if (g_v) wf_load4<ALIGNED>(g_v + 2 * ip, ga[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < DW_G; ++q) {
+            const int b = min(bg + q, b1 - 1);
+            float g[2] = {gg[q][0], gg[q][1]};
+            if (g_p) {
+                float acc[2] = {0.0f, 0.0f};
+#pragma unroll
+                for (int n4 = 0; n4 < NP; n4 += 4) {
+                    const f32x4 gq = *(const f32x4 *)&gp[b - b0][n4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        acc[0] = __builtin_fmaf(gq[u], wk[n4 + u][0], acc[0]);
+                        acc[1] = __builtin_fmaf(gq[u], wk[n4 + u][1], acc[1]);
+                    }
+                }
+                g[0] += acc[0], g[1] += acc[1];
+            }
+            float o[4];
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                const float pv0 = sigmoidf_dev(vv[q][2 * p]), pv1 = sigmoidf_dev(vv[q][2 * p + 1]);
+                const bool right = pv1 > pv0;
+                const float g0 = right ? 0.0f : g[p], g1 = right ? g[p] : 0.0f;
+                o[2 * p] = g0 * pv0 * (1.0f - pv0);
+                o[2 * p + 1] = g1 * pv1 * (1.0f - pv1);
+            }
+            if (g_v) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) o[j] += ga[q][j];
+            }
+            if (bg + q < b1) {
+                float *op = gvf + 2 * ((long)b * K + k);
+                if constexpr (ALIGNED) {
+                    *(f32x4 *)op = f32x4{o[0], o[1], o[2], o[3]};
+                } else {
+                    op[0] = o[0], op[1] = o[1], op[2] = o[2], op[3] = o[3];
+                }
+            }
+        }
+    }
+}
+
+// the dv launch of a backward call of that geometry (dcll_bwd_w3_check passed).  *form = the kernel's name for the launch log,
+// nullptr = not served (target > 32, or more batch chunks than a grid's y takes): the caller keeps k_bwd_dv
+int dcll_launch_bwd_dv_w3(const dcll_conv_desc *d, const float *v, const float *g_p, const float *g_pv, const float *g_v,
+                          const float *i2o_W, float *gvf, int32_t B, hipStream_t st, const char **form)
+{
+    static_assert(DW_PB >= 1 && DW_PB % DW_G == 0, "a chunk is whole groups of samples in flight");
+    *form = nullptr;
+    const long K = 32L * d->h * d->w;                      // 64 channels x h x w / 2 pooled positions; % 1024 == 0
+    const long nby = ((long)B + DW_PB - 1) / DW_PB;
+    if (d->target > 32 || nby > 65535) return DCLL_OK;
+    if (d->c_out != 64 || d->pool_h != 1 || d->pool_w != 2 || (d->w & 1) || K % DW_POS != 0 || K > 0x7fffffffL / 2 || !v || !gvf ||
+        (g_p && !i2o_W))
+        return fail(DCLL_ERR_LAUNCH, "k_bwd_dv_w3: launch layout outside the predicate's", "dcll_conv_lif_backward_w3_ex");
+    const bool aligned = ((((uintptr_t)v | (uintptr_t)gvf | (uintptr_t)g_v) & 15) | (((uintptr_t)g_pv | (uintptr_t)i2o_W) & 7)) == 0;
+    const dim3 grid((unsigned)(K / DW_POS), (unsigned)nby);
+#define DCLL_DVW3(NP_)                                                                                                  \
+    do {                                                                                                                \
+        if (aligned)                                                                                                    \
+            hipLaunchKernelGGL((k_bwd_dv_w3<NP_, true>), grid, dim3(DW_THREADS), 0, st, (int)K, d->target, v, g_p, g_pv, g_v,   \
+                               i2o_W, gvf, B);                                                                          \
+        else                                                                                                            \
+            hipLaunchKernelGGL((k_bwd_dv_w3<NP_, false>), grid, dim3(DW_THREADS), 0, st, (int)K, d->target, v, g_p, g_pv, g_v,  \
+                               i2o_W, gvf, B);                                                                          \
+    } while (0)
+    if (d->target <= 8) DCLL_DVW3(8);
+    else if (d->target <= 16) DCLL_DVW3(16);
+    else if (d->target <= 24) DCLL_DVW3(24);
+    else DCLL_DVW3(32);
+#undef DCLL_DVW3
+    *form = aligned ? "k_bwd_dv_w3" : "k_bwd_dv_w3 (unaligned)";
+    return DCLL_OK;
+}

@@ -1168,6 +1168,8 @@ class DCLLBase(nn.Module):
     w3_learning_path = False        # _learn_tail: dcll_conv_lif_backward_w3[_open] (k_bwd_wgrad_w3); set by ConvNetwork.w3_step_path
     w3_first_wgrad = False          # with w3_learning_path: dcll_conv_lif_backward_w3f[_open] (the c_in 1 layer on k_bwd_wgrad_w3f);
                                     # set by ConvNetwork.w3_first_wgrad
+    w3_dv = False                   # with w3_learning_path: dcll_conv_lif_backward_w3_ex[_open] with DCLL_W3_DV (the dv plane from
+                                    # k_bwd_dv_w3, bit-identical to k_bwd_dv's); set by ConvNetwork.w3_dv_path
 
     def w3_step_supported(self):
         """True if this slice's layer steps and backward can run on k_lif_step_w3 / k_bwd_wgrad_w3
@@ -1234,7 +1236,7 @@ class DCLLBase(nn.Module):
             ops.conv_lif_backward(desc, i2h.state.eps1, v, pv, g_p, g_o, None, None, L.i2o.weight,
                                   want_out=L.output_layer, out=gb, open_reduce=open_reduce,
                                   defer=defer_backward if open_reduce else None, any_path=self.any_learning_path,
-                                  w3_path=self.w3_learning_path, w3_first=self.w3_first_wgrad)
+                                  w3_path=self.w3_learning_path, w3_first=self.w3_first_wgrad, w3_dv=self.w3_dv)
         return loss
 
     def _grads_into_slab(self):

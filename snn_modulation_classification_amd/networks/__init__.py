@@ -307,7 +307,7 @@ class ConvNetwork(torch.nn.Module):
             walk(s.__dict__.get('_learn_bufs', {}))
             sig.append(bool(s.any_learning_path))
             sig.append(bool(L.i2h.any_step_path))
-            sig.append((bool(s.w3_learning_path), bool(L.i2h.w3_step_path), bool(s.w3_first_wgrad)))
+            sig.append((bool(s.w3_learning_path), bool(L.i2h.w3_step_path), bool(s.w3_first_wgrad), bool(s.w3_dv)))
             for t in s._adam_tensors(advance=False):
                 sig += [t['param'].data_ptr(), t['grad'].data_ptr(), t['exp_avg'].data_ptr(),
                         t['exp_avg_sq'].data_ptr(), t['weight_decay'], t['beta1'], t['beta2'], t['eps']]
@@ -942,6 +942,7 @@ class ConvNetwork(torch.nn.Module):
             s.dclllayer.i2h.w3_step_path = on
             if not on:
                 s.w3_first_wgrad = False        # (it rides on the w3 path)
+                s.w3_dv = False                 # (likewise)
 
     @property
     def w3_first_wgrad(self):
@@ -959,6 +960,23 @@ class ConvNetwork(torch.nn.Module):
             raise ops._lib.DCLLUnsupported('w3_first_wgrad needs w3_step_path (set it first)')
         for s in self.dcll_slices:              # (part of _graph_signature: a captured timestep of the other path is retaken)
             s.w3_first_wgrad = on
+
+    @property
+    def w3_dv_path(self):
+        """True: with w3_step_path, every layer's backward takes its dv plane from k_bwd_dv_w3 (a streaming form of k_bwd_dv for
+        the (1,2) pooling of these layers; dcll_conv_lif_backward_w3_ex[_open] with DCLL_W3_DV) instead of the generic k_bwd_dv.
+        The plane is bit-identical, so spikes, state, every gradient and the parameters after Adam are the bits of the same network
+        without it.  Independent of w3_first_wgrad.  Default False; setting it True while w3_step_path is off raises
+        DCLLUnsupported and leaves it off; w3_step_path = False clears it; switching it off is always allowed."""
+        return all(s.w3_dv for s in self.dcll_slices)
+
+    @w3_dv_path.setter
+    def w3_dv_path(self, on):
+        on = bool(on)
+        if on and not self.w3_step_path:
+            raise ops._lib.DCLLUnsupported('w3_dv_path needs w3_step_path (set it first)')
+        for s in self.dcll_slices:              # (part of _graph_signature: a captured timestep of the other path is retaken)
+            s.w3_dv = on
 
     # -- the fused path of any plain conv network (k_lif_seq_any, ABI 8): opt-in, beside test_sequence ---------------------
     def sequence_any_supported(self):

@@ -267,10 +267,11 @@ def backward_any_supported(desc):
 
 BWD_ANY_MAX_CHUNKS = 256        # batch chunks (partial rows) of k_bwd_wgrad_any, at most
 BWD_W3F_PB = 128                # pixels of a job of k_bwd_wgrad_w3f (the flattened B x h w stream): at most one partial row per job
+W3_FIRST_WGRAD, W3_DV = 1, 2    # flag bits of dcll_conv_lif_backward_w3_ex[_open] (DCLL_W3_FIRST_WGRAD, DCLL_W3_DV)
 
 
 def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want_out, out=None, open_reduce=False, defer=None,
-                      any_path=False, w3_path=False, w3_first=False):
+                      any_path=False, w3_path=False, w3_first=False, w3_dv=False):
     """Gradients of one layer step (dcll_conv_lif_backward) -> (dW, db, d_outW, d_outb).  `out`: optional dict with
     preallocated 'dW', 'db', 'd_outW', 'd_outb', 'bwd_scratch' (the learning loop writes into the parameters' .grad).
     `open_reduce`: dcll_conv_lif_backward_open — dW / db are NOT written yet; the partial rows of the weight gradient stay
@@ -282,11 +283,16 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
     `w3_path`: dcll_conv_lif_backward_w3[_open] — the weight gradient of a 64 -> 64 layer of the (1,3) / (1,2)-pool geometry on
     k_bwd_wgrad_w3 (fp32 MFMA; backward_w3_supported); `defer` as for `any_path`; combined with `any_path` it raises.
     `w3_first` (with `w3_path`; alone it raises): dcll_conv_lif_backward_w3f[_open] — the same, and the first layer of that geometry
-    (c_in 1) takes its weight gradient from k_bwd_wgrad_w3f (a streaming reduction) instead of the generic k_bwd_wgrad."""
+    (c_in 1) takes its weight gradient from k_bwd_wgrad_w3f (a streaming reduction) instead of the generic k_bwd_wgrad.
+    `w3_dv` (with `w3_path`; alone it raises; independent of `w3_first`): dcll_conv_lif_backward_w3_ex[_open] with DCLL_W3_DV — the
+    dv plane from k_bwd_dv_w3 instead of k_bwd_dv, bit for bit the same plane (a layer with more than 32 readout rows keeps
+    k_bwd_dv); the scratch size is unchanged."""
     if w3_path and any_path:
         raise ValueError("conv_lif_backward(w3_path=True) cannot be combined with any_path=True")
     if w3_first and not w3_path:
         raise ValueError("conv_lif_backward(w3_first=True) needs w3_path=True")
+    if w3_dv and not w3_path:
+        raise ValueError("conv_lif_backward(w3_dv=True) needs w3_path=True")
     B = eps1.shape[0]
     dev = eps1.device
     out = {} if out is None else out
@@ -331,6 +337,9 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
     # gradients in one call would then alias)
     gp_, go_, gpv_, gv_ = c(g_p), (c(g_o) if want_out else None), c(g_pv), c(g_v)
     fn = "dcll_conv_lif_backward_w3f" if w3_first else "dcll_conv_lif_backward_w3" if w3_path else "dcll_conv_lif_backward_any" if any_path else "dcll_conv_lif_backward"
+    flags = ()
+    if w3_dv:       # (the flag-word entry points; without w3_dv the calls above are made as before)
+        fn, flags = "dcll_conv_lif_backward_w3_ex", (W3_DV | (W3_FIRST_WGRAD if w3_first else 0),)
     if defer is not None and not any_path and not w3_path:       # (open form, launched later with other layers': conv_lif_backward_open_multi)
         item = _lib.BwdItem(ctypes.pointer(desc), ptr(eps1), ptr(v), ptr(pv_pooled), ptr(gp_), ptr(go_), ptr(gpv_), ptr(gv_),
                             ptr(i2o_W), ptr(d_outW), ptr(d_outb), ptr(scratch), n_scratch, B, 0, None, 0, 0)
@@ -342,7 +351,7 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
         rc = getattr(_lib.get(), fn + "_open")(
             ctypes.byref(desc), ptr(eps1), ptr(v), ptr(pv_pooled), ptr(gp_), ptr(go_),
             ptr(gpv_), ptr(gv_), ptr(i2o_W), ptr(d_outW), ptr(d_outb), ptr(scratch), n_scratch, B,
-            ctypes.byref(part), ctypes.byref(nchunk), stream_ptr())
+            ctypes.byref(part), ctypes.byref(nchunk), *flags, stream_ptr())
         check(rc, fn + "_open")
         out['parts'] = dict(part=part.value, nchunk=nchunk.value, c_out=desc.c_out,
                             rowlen=(desc.c_in // desc.groups) * desc.kh * desc.kw + 1, dW=dW, db=db, keep=scratch)
@@ -350,7 +359,7 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
     rc = getattr(_lib.get(), fn)(
         ctypes.byref(desc), ptr(eps1), ptr(v), ptr(pv_pooled), ptr(gp_), ptr(go_),
         ptr(gpv_), ptr(gv_), ptr(i2o_W), ptr(dW), ptr(db), ptr(d_outW), ptr(d_outb), ptr(scratch), n_scratch, B,
-        stream_ptr())
+        *flags, stream_ptr())
     check(rc, fn)
     return dW, db, d_outW, d_outb
 

@@ -108,6 +108,15 @@ def parse_args(argv=None):
                         'layer 0\'s open backward call 1294.6-1298.8 -> 865.1-867.9 us, net.learn 4.083-4.110 -> 3.665-3.688 ms '
                         '(1.11-1.12x); at B = 64 the call 176.6-179.9 -> 102.9-104.9 us, net.learn 1.116-1.185 -> 1.034-1.442 ms: '
                         'ranges overlap, not claimed faster.  Table: profiles/r14_w3f_wgrad_timing.txt')
+    p.add_argument('--w3_dv_path', action='store_true',
+                   help='opt in, effective only together with --w3_step_path on a network it serves: every layer\'s backward takes '
+                        'its dv plane from k_bwd_dv_w3 (a streaming form of k_bwd_dv for the (1,2) pooling: two pooled positions per '
+                        'thread, readout weights in registers) instead of the generic k_bwd_dv; the plane, and with it every '
+                        'gradient, is bit-identical; ignored with a notice elsewhere.  Measured on an MI355X, (16,128) plane, with --w3_step_path '
+                        '--w3_first_wgrad in both arms, five alternating fresh processes, min-max: net.learn 3.689-3.709 -> 2.263-2.271 ms '
+                        'per timestep at B = 512 (1.62-1.64x), 1.050-1.088 -> 0.883-0.913 ms at B = 64 (1.15-1.23x); layer 0\'s dv kernel '
+                        '829.5 -> 100.1 us at B = 512 (0.85 of the copy rate); the open backward call of every one of the seven layers is '
+                        'faster at both batch sizes, none slower.  Table: profiles/r15_w3_dv_timing.txt')
     p.add_argument('--gpus', type=int, default=1, metavar='N',
                    help='ranks (one process per GPU): every batch is sharded over them, the local-learning gradients are '
                         'averaged over the ranks every timestep (one bucketed all-reduce)')
@@ -335,20 +344,27 @@ def _opt_in_any_step(net, args):
 
 def _opt_in_w3_step(net, args):
     """--w3_step_path: switch the network's per-step layer calls and weight gradients to k_lif_step_w3 / k_bwd_wgrad_w3 where
-    every layer is served; --w3_first_wgrad with it: the first layer's weight gradient on k_bwd_wgrad_w3f."""
-    first = getattr(args, 'w3_first_wgrad', False)
+    every layer is served; --w3_first_wgrad with it: the first layer's weight gradient on k_bwd_wgrad_w3f; --w3_dv_path with it:
+    every layer's dv plane from k_bwd_dv_w3."""
+    first, dv = getattr(args, 'w3_first_wgrad', False), getattr(args, 'w3_dv_path', False)
     if not args.w3_step_path:
         if first:
             print('--w3_first_wgrad ignored: it rides on --w3_step_path, which is not given')
+        if dv:
+            print('--w3_dv_path ignored: it rides on --w3_step_path, which is not given')
         return
     if net.w3_step_supported():
         net.w3_step_path = True
         if first:
             net.w3_first_wgrad = True
+        if dv:
+            net.w3_dv_path = True
     else:
         print('--w3_step_path ignored: k_lif_step_w3 / k_bwd_wgrad_w3 do not serve every layer of this network')
         if first:
             print('--w3_first_wgrad ignored: --w3_step_path is not in effect on this network')
+        if dv:
+            print('--w3_dv_path ignored: --w3_step_path is not in effect on this network')
 
 
 def main_mnist(args):
