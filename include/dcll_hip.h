@@ -533,6 +533,30 @@ int dcll_pack_spike_planes(const float *dense, uint32_t *packed, int64_t n_plane
 int dcll_unpack_spike_planes(const uint32_t *packed, float *dense, int64_t n_planes, int32_t hw, void *stream);
 
 /*
+ * Still ABI 10 (three more symbols, found by lookup) — dcll_conv_lif_sequence_any for layers of up to 64 output channels
+ * (k_lif_seq_wide): the fused all-T path of the networks a --netscale above 1 makes (radio_ml_conv.yaml at netscale 2 on 16x16:
+ * 1 -> 64, 64 -> 64; mnist_conv.yaml at netscale 2: 32 / 48 / 64 channels).  Arguments, buffer formats, arithmetic and results
+ * are dcll_conv_lif_sequence_any's.  Additions only: the calls above, their refusals and their kernels are unchanged.
+ * MT = ceil(c_out / 32) tiles of 32 MFMA rows:
+ *   MT = 1  the call is handed to dcll_conv_lif_sequence_any unchanged (its kernels, launch-log names, bits, _lds and _scratch)
+ *   MT = 2  k_lif_seq_wide: a wave runs both 32-row chains of a pixel tile, interleaved, each the pinned chain, unsplit.
+ *     LDS form       4 bytes x (c_in (h + 2 pad_h)(w + 2 pad_w) + c_in h w + c_out ch cw + c_out ch cw [arp, refractory layers
+ *                    only] + 4 c_in + 64) <= 160 KiB; or, beyond that,
+ *     register form  layers WITHOUT pooling with c_in h w <= 18432 and ch cw <= 256: LDS holds 4 bytes x (c_in (h + 2 pad_h)
+ *                    (w + 2 pad_w) + 4 c_in + 64) <= 160 KiB.
+ *     w_scratch      dcll_conv_lif_sequence_wide_scratch(d) = 128 floats per MFMA step of a chain, written by k_seq_wide_wprep
+ *                    in front of the layer kernel on every call.
+ * DCLL_ERR_UNSUPPORTED, before any launch: c_out > 64, stride / dilation / groups other than 1, a kernel beyond 16x16, a working
+ * set beyond both forms.  DCLL_ERR_INVALID, before any launch: a NULL required pointer, a refractory layer without arp, T < 0 or
+ * B < 0.  T == 0 or B == 0: DCLL_OK, nothing is looked at.  _lds: LDS bytes of the form that serves the layer, 0 = refused.
+ */
+int64_t dcll_conv_lif_sequence_wide_lds(const dcll_conv_desc *d);
+int64_t dcll_conv_lif_sequence_wide_scratch(const dcll_conv_desc *d);
+int dcll_conv_lif_sequence_wide(const dcll_conv_desc *d, const uint32_t *spk_in, const float *W, const float *b,
+                                const float *tau4, float *eps0, float *eps1, float *arp, uint32_t *spk_out, float *pv_out,
+                                float *v_out, float *w_scratch, int32_t T, int32_t B, void *stream);
+
+/*
  * ABI 9 — the backward of one layer step with the weight gradient of ANY plain conv layer on fp32-MFMA tiles (k_bwd_wgrad_any):
  * dcll_conv_lif_backward / dcll_conv_lif_backward_open with the same arguments, results and scratch rule (B c_out ch cw +
  * k (c_out (c_in kh kw + 1)) floats, k >= 1; less: DCLL_ERR_INVALID), for the layers whose weight gradient the calls above

@@ -872,11 +872,22 @@ def sequence_any_supported(desc):
     return sequence_any_lds(desc) > 0
 
 
-def conv_lif_sequence_any(desc, spk_in, W, b, tau4, eps0, eps1, arp, T, B, want_spikes=True, want_pv=True, want_v=False,
-                          out=None):
-    """All T steps of any plain conv layer in one launch (k_lif_seq_any).  spk_in (T,B,c_in,ceil(h*w/32)) int32 spike
-    planes (pack_spike_planes) -> (pooled spikes (T,B,c_out,ceil(ph*pw/32)) int32, pv (T,B,c_out,ph,pw), v (T,B,c_out,ch,cw)),
-    each None when not wanted.  `out`: optional dict of reusable buffers 'spk' / 'pv' / 'w_scratch'."""
+def sequence_wide_lds(desc):
+    """LDS bytes per sample of the kernel dcll_conv_lif_sequence_wide runs on this layer (k_lif_seq_wide for 33-64 output
+    channels, k_lif_seq_any up to 32), 0 = the layer is not served (dcll_conv_lif_sequence_wide_lds; host-only)."""
+    return int(_lib.get().dcll_conv_lif_sequence_wide_lds(ctypes.byref(desc)))
+
+
+def sequence_wide_supported(desc):
+    """True if dcll_conv_lif_sequence_wide serves the layer: a plain conv with c_out <= 64, a kernel up to 16x16 and a
+    per-sample working set within one of the kernel's two forms (include/dcll_hip.h)."""
+    return sequence_wide_lds(desc) > 0
+
+
+def _conv_lif_sequence_call(call, scratch_floats, what, desc, spk_in, W, b, tau4, eps0, eps1, arp, T, B, want_spikes, want_pv,
+                            want_v, out):
+    """The body shared by conv_lif_sequence_any / conv_lif_sequence_wide: `call` and `scratch_floats` are the bound C functions
+    (the layer call and its _scratch), `what` names the call in an error."""
     dev = W.device
     out = {} if out is None else out
     ch, cw, ph, pw = conv_out_shape(desc)
@@ -892,15 +903,36 @@ def conv_lif_sequence_any(desc, spk_in, W, b, tau4, eps0, eps1, arp, T, B, want_
     _expect(spk, "spk_out", torch.int32, (T, B, desc.c_out, ow))
     _expect(pv, "pv_out", torch.float32, (T, B, desc.c_out, ph, pw))
     v = torch.empty((T, B, desc.c_out, ch, cw), device=dev, dtype=torch.float32) if want_v else None
-    n = int(_lib.get().dcll_conv_lif_sequence_any_scratch(ctypes.byref(desc)))
+    n = int(scratch_floats(ctypes.byref(desc)))
     scratch = out.get("w_scratch")
     if scratch is None or scratch.numel() < n or scratch.device != dev:
         scratch = out["w_scratch"] = torch.empty((n,), device=dev, dtype=torch.float32)
     _expect(scratch, "w_scratch", torch.float32)
-    rc = _lib.get().dcll_conv_lif_sequence_any(ctypes.byref(desc), ptr(spk_in), ptr(W), ptr(b), ptr(tau4), ptr(eps0), ptr(eps1),
-                                               ptr(arp), ptr(spk), ptr(pv), ptr(v), ptr(scratch), T, B, stream_ptr())
-    check(rc, "dcll_conv_lif_sequence_any")
+    rc = call(ctypes.byref(desc), ptr(spk_in), ptr(W), ptr(b), ptr(tau4), ptr(eps0), ptr(eps1), ptr(arp), ptr(spk), ptr(pv), ptr(v),
+              ptr(scratch), T, B, stream_ptr())
+    check(rc, what)
     return spk, pv, v
+
+
+def conv_lif_sequence_any(desc, spk_in, W, b, tau4, eps0, eps1, arp, T, B, want_spikes=True, want_pv=True, want_v=False,
+                          out=None):
+    """All T steps of any plain conv layer in one launch (k_lif_seq_any).  spk_in (T,B,c_in,ceil(h*w/32)) int32 spike
+    planes (pack_spike_planes) -> (pooled spikes (T,B,c_out,ceil(ph*pw/32)) int32, pv (T,B,c_out,ph,pw), v (T,B,c_out,ch,cw)),
+    each None when not wanted.  `out`: optional dict of reusable buffers 'spk' / 'pv' / 'w_scratch'."""
+    lib = _lib.get()
+    return _conv_lif_sequence_call(lib.dcll_conv_lif_sequence_any, lib.dcll_conv_lif_sequence_any_scratch,
+                                   "dcll_conv_lif_sequence_any", desc, spk_in, W, b, tau4, eps0, eps1, arp, T, B, want_spikes,
+                                   want_pv, want_v, out)
+
+
+def conv_lif_sequence_wide(desc, spk_in, W, b, tau4, eps0, eps1, arp, T, B, want_spikes=True, want_pv=True, want_v=False,
+                           out=None):
+    """conv_lif_sequence_any through dcll_conv_lif_sequence_wide: layers of up to 64 output channels (k_lif_seq_wide above 32,
+    k_lif_seq_any itself up to 32).  Same arguments, buffers and results."""
+    lib = _lib.get()
+    return _conv_lif_sequence_call(lib.dcll_conv_lif_sequence_wide, lib.dcll_conv_lif_sequence_wide_scratch,
+                                   "dcll_conv_lif_sequence_wide", desc, spk_in, W, b, tau4, eps0, eps1, arp, T, B, want_spikes,
+                                   want_pv, want_v, out)
 
 
 LOSS_KINDS = {"SmoothL1Loss": _lib.LOSS_SMOOTH_L1, "MSELoss": _lib.LOSS_MSE}

@@ -78,6 +78,16 @@ def parse_args(argv=None):
                    help='opt in: the test phase of a network without a geometry-specialised sequence kernel '
                         '(sequence_supported() False, e.g. --data MNIST with mnist_conv.yaml, or RadioML on a 24x24 plane) runs '
                         'ConvNetwork.test_sequence_any (k_lif_seq_any) where it serves every layer, instead of net.test per timestep')
+    p.add_argument('--wide_sequence_path', action='store_true',
+                   help='opt in: --any_sequence_path through dcll_conv_lif_sequence_wide — the test phase of a network without a '
+                        'geometry-specialised sequence kernel runs ConvNetwork.test_sequence_any(wide=True): k_lif_seq_wide for '
+                        'layers of 33-64 output channels (--netscale up to 2), k_lif_seq_any up to 32; one process only; ignored '
+                        'with a notice where the network is not served.  Measured on an MI355X against the per-step loop, five '
+                        'alternating fresh processes, min-max ms per sequence: radio_ml_conv.yaml at netscale 2 on 16x16, T = 128: '
+                        '343.10-343.87 -> 167.33-167.67 at B = 512 (2.05x), but NOT faster at B = 64: 62.59-62.97 -> 82.96-83.44 '
+                        '(one workgroup per sample leaves CUs idle below 256 samples); mnist_conv.yaml at netscale 2, T = 50: '
+                        '15.78-15.98 -> 13.62-13.76 at B = 32 (1.15x), 79.00-79.60 -> 29.03-29.09 at B = 512 (2.72x) (DESIGN 4.1e; '
+                        'experiments/seq_wide_timing.py)')
     p.add_argument('--any_learning_path', action='store_true',
                    help='opt in: every layer\'s weight gradient of the learning step runs on k_bwd_wgrad_any (fp32 MFMA; any '
                         'plain conv layer with c_out <= 32 and a kernel up to 16x16, which lifts the default path\'s 64-tap '
@@ -212,6 +222,9 @@ def main(argv=None):
     # --any_sequence_path: a network without a specialised sequence kernel is tested on k_lif_seq_any (one process only; several
     # ranks keep evaluate_batch's sharded per-step evaluation)
     use_any = args.any_sequence_path and not use_sequence and world == 1 and net.sequence_any_supported()
+    # --wide_sequence_path: the same with wide=True (layers of up to 64 output channels: a --netscale up to 2)
+    use_wide = _opt_in_wide_sequence(net, args, use_sequence, world)
+    use_any = use_any or use_wide
 
     def evaluate_batch_any(samples, labels1h):
         """The per-step branch of evaluate_batch (host-encoded planes, reference test_radio_ml.py:142-146) with its T-loop replaced
@@ -222,7 +235,7 @@ def main(argv=None):
                                         max_Q=args.Q_bounds[1], max_duration=T)
         net.reset()
         net.eval()
-        net.test_sequence_any(torch.Tensor(spikes).to(pytorch_libdcll.device)[:T])
+        net.test_sequence_any(torch.Tensor(spikes).to(pytorch_libdcll.device)[:T], wide=use_wide)
         return net.accuracy(torch.as_tensor(np.asarray(targets), dtype=torch.float32))
 
     def run_tests(step):
@@ -322,6 +335,24 @@ def main(argv=None):
     return out_dir
 
 
+def _opt_in_wide_sequence(net, args, use_sequence, world=1):
+    """--wide_sequence_path: True where the test phase runs ConvNetwork.test_sequence_any(wide=True) — the caller's test phase
+    does not run the specialised sequence kernels (use_sequence False), one process, every layer served by
+    dcll_conv_lif_sequence_wide; elsewhere a notice and the default path."""
+    if not args.wide_sequence_path:
+        return False
+    if use_sequence:
+        why = 'the network runs its geometry-specialised sequence kernels'
+    elif world > 1:
+        why = 'several ranks keep the sharded per-step evaluation'
+    elif not net.sequence_any_supported(wide=True):
+        why = 'dcll_conv_lif_sequence_wide does not serve every layer of this network'
+    else:
+        return True
+    print('--wide_sequence_path ignored: ' + why)
+    return False
+
+
 def _opt_in_any_learning(net, args):
     """--any_learning_path: switch the network's learning step to k_bwd_wgrad_any where every slice is served."""
     if not args.any_learning_path:
@@ -393,6 +424,7 @@ def main_mnist(args):
     _opt_in_any_learning(net, args)
     _opt_in_any_step(net, args)
     _opt_in_w3_step(net, args)
+    use_wide = _opt_in_wide_sequence(net, args, net.sequence_supported())      # (the condition of --any_sequence_path below)
     parallel.freeze_startup_heap()          # (a full GC pass over the start-up heap costs ~100 ms inside the T-loop)
     n_test = int(np.ceil(float(args.n_test_samples) / args.batch_size_test))
     if args.synthetic:
@@ -444,7 +476,9 @@ def main_mnist(args):
                 tx, ty = spikes_of(ts, tl, st_test)
                 net.reset()
                 net.eval()
-                if args.any_sequence_path and not net.sequence_supported() and net.sequence_any_supported():
+                if use_wide:
+                    net.test_sequence_any(tx[:args.n_iters_test], wide=True)
+                elif args.any_sequence_path and not net.sequence_supported() and net.sequence_any_supported():
                     net.test_sequence_any(tx[:args.n_iters_test])
                 else:
                     for t in range(args.n_iters_test):
