@@ -25,6 +25,9 @@
  *                       nesting order, zero padding contributing fmaf(0, w, acc); one rounding per product
  *       arp' = alpharp*arp ; v = pvmem + arp' ; s = v > 0 ; arp'' = arp' - s*wrp     (refractory variant)
  *       pv = 1/(1+exp(-v)) (not bit-pinned) ; readouts p,o fp32 (not bit-pinned; |err| <= 1e-4)
+ *     value domain (tests/test_gpu_values.py): fp32 subnormals are kept in state, operands and results — nothing flushes;
+ *     s = v > 0 holds for every finite v, +-0 and subnormals included; pv is finite and inside [0, 1] for every finite v.
+ *     NaN and Inf inputs are unspecified.
  */
 #ifndef DCLL_HIP_H
 #define DCLL_HIP_H

@@ -22,10 +22,10 @@
 
 constexpr int DN_BT = 128, DN_KC = 32, DN_LD = 34;
 
-// 4 consecutive floats of row `row` (nrows rows of n floats) from column k0, zeros outside; float4 when it is aligned
-__device__ __forceinline__ f32x4 dn_load4(const float *__restrict__ m, long row, long nrows, int n, int k0, bool vec)
+// 4 consecutive floats of row `row` (nrows rows of n floats) from column k0, `pad` outside; float4 when it is aligned
+__device__ __forceinline__ f32x4 dn_load4(const float *__restrict__ m, long row, long nrows, int n, int k0, bool vec, float pad = 0.f)
 {
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    f32x4 v = {pad, pad, pad, pad};
     if (row < nrows) {
         const float *p = m + row * n + k0;
         if (vec && k0 + 3 < n) {
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(256) void k_dense_lif_mfma(int in, int out, const f
 #pragma unroll
         for (int q = 0; q < 4; ++q) re[S][q] = dn_load4(eps1, b0 + r + 32 * q, B, in, k0 + c4, vec);
 #pragma unroll
-        for (int q = 0; q < NTW; ++q) rw[S][q] = dn_load4(W, o0 + r + 32 * q, out, in, k0 + c4, vec);
+        for (int q = 0; q < NTW; ++q) rw[S][q] = dn_load4(W, o0 + r + 32 * q, out, in, k0 + c4, vec, DCLL_PAD_W);
     };
     auto store = [&](auto setc) {                           // register set S -> LDS buffer S
         constexpr int S = decltype(setc)::value;
@@ -283,7 +283,7 @@ __global__ __launch_bounds__(256) void k_dense_lif_seq(int in, int out, const fl
         f32x4 rw[4];
         auto fetch = [&](int k0) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) rw[q] = dn_load4(W, r + 32 * q, out, in, k0 + c4, vec);
+            for (int q = 0; q < 4; ++q) rw[q] = dn_load4(W, r + 32 * q, out, in, k0 + c4, vec, DCLL_PAD_W);
         };
         fetch(0);
         for (int k0 = 0; k0 < in; k0 += DS_KC) {

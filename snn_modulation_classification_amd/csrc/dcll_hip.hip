@@ -219,7 +219,7 @@ __global__ __launch_bounds__(256) void k_conv_lif_tiled(dcll_conv_desc d, int ch
         }
         for (int i = tid; i < COG * KK * 2; i += 256) {
             const int hh = i & 1, tap = (i >> 1) % KK, c = (i >> 1) / KK, ci = 2 * cp + hh;
-            wl[i] = (co0 + c < d.c_out && ci < d.c_in) ? W.at(((long)(co0 + c) * d.c_in + ci) * KK + tap, co0 + c) : 0.0f;
+            wl[i] = (co0 + c < d.c_out && ci < d.c_in) ? W.at(((long)(co0 + c) * d.c_in + ci) * KK + tap, co0 + c) : DCLL_PAD_W;
         }
         __syncthreads();
         float win[2][KK];
@@ -1180,9 +1180,9 @@ constexpr int C1_MAXT = 4096;       // longest window the fused IQ encoder of k_
 // loads of the I and the Q row of this window) and parks the cell index of step t in LDS.
 //
 // Conv as fp32 MFMA, weight-stationary: the K = 49 taps in their pinned linear order (ky, kx) are paired two by two over
-// the MFMA's k lanes — pair p = taps (2p, 2p+1), 25 MFMAs per tile, only tap 49 is padding (ZERO weight:
-// fmaf(x, 0, acc) == acc, so every channel still sees the chain bias, tap 0, tap 1, ... tap 48).  A = weights (lane: co =
-// lane&31, tap parity = lane>>5; 25 VGPRs for the whole sequence), B = eps1 from a zero-padded 22x24 LDS plane: lane h = 1
+// the MFMA's k lanes — pair p = taps (2p, 2p+1), 25 MFMAs per tile, only tap 49 is padding (weight DCLL_PAD_W = -0:
+// fmaf(x, -0, acc) == acc for every acc when x >= +0, so every channel still sees the chain bias, tap 0, tap 1, ... tap 48).
+// A = weights (lane: co = lane&31, tap parity = lane>>5; 25 VGPRs for the whole sequence), B = eps1 from a zero-padded 22x24 LDS plane: lane h = 1
 // reads one float behind lane h = 0, except for the three pairs whose second tap starts the next kernel row (p = 3, 10,
 // 17: PS - 6 floats behind) — two per-lane bases + immediates.  (Round 1 padded every kernel row to 4 pairs: 28 MFMAs.)
 // D[co][pixel]; 4 waves = 8 pixel tiles of 32 (wave w: image rows 4w..4w+3); a thread also owns pixel `tid` of the traces.
@@ -1226,12 +1226,12 @@ __global__ __launch_bounds__(256, 3) void k_lif_seq_c1(int c_out, const int32_t 
         }
     }
     float e0 = eps0_g[(long)b * 256 + pix], e1 = eps1_g[(long)b * 256 + pix];
-    // weight fragments: pair p: lane (co = j, tap = 2p + h); the pad tap and channels >= c_out carry 0
+    // weight fragments: pair p: lane (co = j, tap = 2p + h); the pad tap and channels >= c_out carry DCLL_PAD_W
     float wf[25];
 #pragma unroll
     for (int p = 0; p < 25; ++p) {
         const int tap = 2 * p + h;
-        wf[p] = (tap < 49 && j < c_out) ? W.at(j * 49 + tap, j) : 0.0f;
+        wf[p] = (tap < 49 && j < c_out) ? W.at(j * 49 + tap, j) : DCLL_PAD_W;
     }
     // refractory trace of my two tiles: arp[tl][r] <-> channel (r&3)+8(r>>2)+4h, pixel 32*(2w+tl) + j
     float arp[2][16];
@@ -1267,7 +1267,7 @@ __global__ __launch_bounds__(256, 3) void k_lif_seq_c1(int c_out, const int32_t 
 #pragma unroll
             for (int p = 0; p < 25; ++p) {
                 const int tap = 2 * p, off = (tap / 7) * PS + tap % 7;
-                const bool cross = (tap % 7 == 6) && p < 24;        // p = 24: the partner is the pad tap (weight 0)
+                const bool cross = (tap % 7 == 6) && p < 24;        // p = 24: the partner is the pad tap (weight -0)
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[p], cross ? bx[off] : bn[off], acc, 0, 0, 0);
             }
             int myword = 0;
@@ -3009,7 +3009,7 @@ __global__ __launch_bounds__(256) void k_trace4(const f32x4 *__restrict__ x, con
 // ------------------------------------------------------------------------------------------------------------
 // k_lif_step_c1 — ONE timestep of the first layer (c_in = 1 -> c_out <= 32 channels, 7x7 pad 3, 16x16 plane, pool 1)
 // for the per-step drop-in and the forward of a learning step: the MFMA form of k_lif_seq_c1 (25 MFMAs per 32-pixel tile,
-// taps paired over the k lanes in their pinned linear order, the pad tap with weight 0) on a dense fp32 input map and
+// taps paired over the k lanes in their pinned linear order, the pad tap with weight -0) on a dense fp32 input map and
 // dense s / pv / v outputs, state through HBM.  One 256-thread workgroup per sample (thread = pixel of the traces, wave w
 // = image rows 4w..4w+3 = two tiles).  The kernel is bound by its maps (160 KB per sample); the generic pair
 // k_trace + k_conv_lif_tiled it replaces ran 98 VALU FMAs per output with LDS weight broadcasts (41 us at B = 512).
@@ -3049,12 +3049,12 @@ __global__ __launch_bounds__(256) void k_lif_step_c1(int c_out, const float *__r
                                             : 0.0f;
             }
     }
-    // weight fragments: pair p: lane (co = j, tap = 2p + h); the pad tap and channels >= c_out carry 0
+    // weight fragments: pair p: lane (co = j, tap = 2p + h); the pad tap and channels >= c_out carry DCLL_PAD_W
     float wf[25];
 #pragma unroll
     for (int p = 0; p < 25; ++p) {
         const int tap = 2 * p + h;
-        wf[p] = (tap < 49 && j < c_out) ? W.at(j * 49 + tap, j) : 0.0f;
+        wf[p] = (tap < 49 && j < c_out) ? W.at(j * 49 + tap, j) : DCLL_PAD_W;
     }
     if (TILED) {
         for (int i = pix; i < 22 * PS + 8; i += 256) {
@@ -3086,7 +3086,7 @@ __global__ __launch_bounds__(256) void k_lif_step_c1(int c_out, const float *__r
 #pragma unroll
         for (int p = 0; p < 25; ++p) {
             const int tap = 2 * p, off = (tap / 7) * PS + tap % 7;
-            const bool cross = (tap % 7 == 6) && p < 24;        // p = 24: the partner is the pad tap (weight 0)
+            const bool cross = (tap % 7 == 6) && p < 24;        // p = 24: the partner is the pad tap (weight -0)
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[p], cross ? bx[off] : bn[off], acc, 0, 0, 0);
         }
 #pragma unroll

@@ -255,10 +255,18 @@ __device__ __forceinline__ float refractory(float pvmem, float &arp, float alpha
     return v;
 }
 
+// The weight of a link that is no link of the pinned chain (the partner of an odd last channel or tap, a K tile's tail): -0, on a
+// trace operand that is +0 or a trace (>= +0).  The product is then -0, and acc + (-0) == acc for EVERY acc, -0 included — a
+// weight of +0 made the product +0 and turned a membrane of -0 into +0 where the oracle, which has no such link, keeps -0
+// (tests/test_gpu_values.py: a bias of -0 under weights of -0).
+constexpr float DCLL_PAD_W = -0.0f;
+
 // (v > 0 ? 1.0f : 0.0f) on a register pair in TWO packed instructions: clamp(clamp(v * 2^127) * 2^127), clamp = the VOP3P
 // clamp to [0, 1].  Exact for every fp32 value a membrane can take — a positive denormal reaches 2^-22 after the first
 // multiplication and 1 after the second (fp32 denormals are on in this build), zeros and negatives clamp to +0
-// (experiments/pk_clamp_probe.hip checks every class on the device).  Replaces 2 v_cmp + 2 v_cndmask in the refractory
+// (tests/test_gpu_values.py: the threshold cases put v on +-0, +-2^-149, +-2^-127 ... +-2^126 in every kernel that uses this, and
+// tests/test_value_cases.py shows that ONE clamp would change arp there; experiments/pk_clamp_probe.hip checks every class of
+// value on the instruction alone).  Replaces 2 v_cmp + 2 v_cndmask in the refractory
 // update s * wrp of the epilogues that share their vector pipe with fp32 MFMAs.
 __device__ __forceinline__ f32x2 spike01_pk(f32x2 v)
 {

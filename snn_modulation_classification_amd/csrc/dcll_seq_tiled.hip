@@ -349,7 +349,7 @@ __global__ __launch_bounds__(512) void k_lif_seq_c32t(const uint32_t *__restrict
 // ------------------------------------------------------------------------------------------------------------
 // k_lif_seq_c1t — the first layer (c_in = 1, one input spike per step as a cell index or raw IQ) on a large plane:
 // one 256-thread workgroup per (sample, 8 x 32 pixel tile), all T steps.  Same MFMA form as k_lif_seq_c1 (49 taps
-// padded per kernel row to 4 k-pairs with a ZERO weight on the pad tap, weight-stationary in 28 VGPRs); the tile's
+// padded per kernel row to 4 k-pairs with a weight of -0 (DCLL_PAD_W) on the pad tap, weight-stationary in 28 VGPRs); the tile's
 // trace region (14 x 38 with the 3-pixel halo, recomputed redundantly like in k_lif_seq_c32t) lives in registers
 // (eps0, eps1: 3 elements per thread) with eps1 mirrored into an LDS plane for the B fragments.
 // ------------------------------------------------------------------------------------------------------------
@@ -414,7 +414,7 @@ __global__ __launch_bounds__(256) void k_lif_seq_c1t(int c_out, const int32_t *_
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int kx = 2 * i + h;
-            wf[ky][i] = (kx < 7 && j < c_out) ? W.at(j * 49 + ky * 7 + kx, j) : 0.0f;
+            wf[ky][i] = (kx < 7 && j < c_out) ? W.at(j * 49 + ky * 7 + kx, j) : DCLL_PAD_W;
         }
     // refractory trace of my two tiles (rows y0 + 2w + tl): arp[tl][r] <-> channel (r&3)+8(r>>2)+4h, column x0 + j
     float arp[2][16];

@@ -346,7 +346,9 @@ def _conv_draw(c, attempt):
     return T
 
 
-def _conv_oracle(c, T):
+def _conv_oracle(c, T, before_step=None):
+    """the oracle over the steps of T['x'] (STEPS of them here; tests/value_cases.py runs up to 8, sets c['alpharp'] and hooks a
+    mutant in front of every step)"""
     from oracle import c_oracle as C
     sd = {"i2h.weight": T["W"], "i2h.alpha": T["tau"][0], "i2h.tau_m__dt": T["tau"][1], "i2h.alphas": T["tau"][2],
           "i2h.tau_s__dt": T["tau"][3], "i2o.weight": T["i2o_W"], "i2o.bias": T["i2o_b"]}
@@ -355,13 +357,15 @@ def _conv_oracle(c, T):
     if c["output_layer"]:
         sd["output_.weight"], sd["output_.bias"] = T["out_W"], T["out_b"]
     orc = C.OracleConvLayer(sd, (c["h"], c["w"]), (c["pad_h"], c["pad_w"]), (c["pool_h"], c["pool_w"]),
-                            1.0 if c["refractory"] else 0.0, ALPHARP, bool(c["output_layer"]), c["stride"], c["dilation"],
-                            c["groups"])
+                            1.0 if c["refractory"] else 0.0, c.get("alpharp", ALPHARP), bool(c["output_layer"]), c["stride"],
+                            c["dilation"], c["groups"])
     assert (orc.ch, orc.cw, orc.ph, orc.pw) == conv_shape(c), (c["id"], "the oracle's output shape differs from the generator's")
     orc.init_state(c["B"])
     orc.state[0][...], orc.state[1][...], orc.state[2][...] = T["eps0"], T["eps1"], T["arp"]
     steps = []
-    for t in range(STEPS):
+    for t in range(len(T["x"])):
+        if before_step is not None:
+            before_step(orc.state)
         o, p, pv, v, s = orc.forward(T["x"][t])
         steps.append(dict(v=v, s=s, pv=pv, p=p, o=(o if c["output_layer"] else None), eps0=orc.state[0].copy(),
                           eps1=orc.state[1].copy(), arp=orc.state[2].copy()))
@@ -430,16 +434,18 @@ def _dense_draw(c, attempt):
     return T
 
 
-def _dense_oracle(c, T):
+def _dense_oracle(c, T, before_step=None):
     from oracle import c_oracle as C
     sd = {"i2h.weight": T["W"], "i2h.alpha": T["tau"][0], "i2h.tau_m__dt": T["tau"][1], "i2h.alphas": T["tau"][2],
           "i2h.tau_s__dt": T["tau"][3], "i2o.weight": T["i2o_W"], "i2o.bias": T["i2o_b"]}
     if T["b"] is not None:
         sd["i2h.bias"] = T["b"]
-    orc = C.OracleDenseLayer(sd, 1.0 if c["refractory"] else 0.0, ALPHARP)
+    orc = C.OracleDenseLayer(sd, 1.0 if c["refractory"] else 0.0, c.get("alpharp", ALPHARP))
     orc.state = [T["eps0"].copy(), T["eps1"].copy(), T["arp"].copy()]
     steps = []
-    for t in range(STEPS):
+    for t in range(len(T["x"])):
+        if before_step is not None:
+            before_step(orc.state)
         s, p, pv, v = orc.forward(T["x"][t])
         steps.append(dict(v=v, s=s, pv=pv, p=p, eps0=orc.state[0].copy(), eps1=orc.state[1].copy(), arp=orc.state[2].copy()))
     return steps

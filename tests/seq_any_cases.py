@@ -272,7 +272,7 @@ def _oracle(c, W, b, tau, wrp):
           "i2o.bias": np.zeros(1, np.float32)}           # (the oracle's own readout is not used: one row of zeros)
     if b is not None:
         sd["i2h.bias"] = b
-    orc = C.OracleConvLayer(sd, (c["h"], c["w"]), (c["pad_h"], c["pad_w"]), (c["pool_h"], c["pool_w"]), wrp, ALPHARP)
+    orc = C.OracleConvLayer(sd, (c["h"], c["w"]), (c["pad_h"], c["pad_w"]), (c["pool_h"], c["pool_w"]), wrp, c.get("alpharp", ALPHARP))
     assert (orc.ch, orc.cw, orc.ph, orc.pw) == (ch, cw, ph, pw), c["id"]
     return orc
 
@@ -315,13 +315,19 @@ def _draw(c, attempt):
     return T
 
 
-def _trajectory(c, T):
-    """the oracle stepping straight through every call -> per call dict(v, s, pv (T, Bc, ...), eps0, eps1, arp after the call)"""
+def _trajectory(c, T, before_step=None):
+    """the oracle stepping straight through every call -> per call dict(v, s, pv (T, Bc, ...), eps0, eps1, arp after the call);
+    before_step(state): run on the oracle's state in front of every step (the mutants of tests/value_cases.py)"""
     orc = _oracle(c, T["W"], T["b"], T["tau"], 1.0 if c["refractory"] else 0.0)
     orc.state = [T["eps0"].copy(), T["eps1"].copy(), T["arp"].copy()]
     out = []
+
+    def one(x):
+        if before_step is not None:
+            before_step(orc.state)
+        return orc.forward(x)           # (o, p, pv, v, s)
     for call in T["calls"]:
-        st = [orc.forward(call["x"][t]) for t in range(call["x"].shape[0])]           # (o, p, pv, v, s)
+        st = [one(call["x"][t]) for t in range(call["x"].shape[0])]
         out.append(dict(v=np.stack([s[3] for s in st]), s=np.stack([s[4] for s in st]), pv=np.stack([s[2] for s in st]),
                         eps0=orc.state[0].copy(), eps1=orc.state[1].copy(), arp=orc.state[2].copy()))
     return out

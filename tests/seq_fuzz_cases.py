@@ -651,9 +651,9 @@ def _sd(c, W, b, tau):
 def _oracle(c, W, b, tau, wrp):
     from oracle import c_oracle as C
     if c["entry"] == "dense":
-        return C.OracleDenseLayer(_sd(c, W, b, tau), wrp, ALPHARP)
+        return C.OracleDenseLayer(_sd(c, W, b, tau), wrp, c.get("alpharp", ALPHARP))
     lay = LAYERS[c["layer"]]
-    orc = C.OracleConvLayer(_sd(c, W, b, tau), (c["h"], c["w"]), lay["pad"], lay["pool"], wrp, ALPHARP)
+    orc = C.OracleConvLayer(_sd(c, W, b, tau), (c["h"], c["w"]), lay["pad"], lay["pool"], wrp, c.get("alpharp", ALPHARP))
     assert (orc.ch, orc.cw, orc.ph, orc.pw) == out_shape(c), c["id"]
     return orc
 
@@ -716,13 +716,19 @@ def _draw(c, attempt):
     return T
 
 
-def _trajectory(c, T):
-    """the oracle stepping straight through every call -> per call dict(v, s, pv (T, Bc, ...), eps0, eps1, arp after the call)"""
+def _trajectory(c, T, before_step=None):
+    """the oracle stepping straight through every call -> per call dict(v, s, pv (T, Bc, ...), eps0, eps1, arp after the call);
+    before_step(state): run on the oracle's state in front of every step (the mutants of tests/value_cases.py)"""
     orc = _oracle(c, T["W"], T["b"], T["tau"], 1.0 if c["refractory"] else 0.0)
     orc.state = [T["eps0"].copy(), T["eps1"].copy(), T["arp"].copy()]
     out = []
+
+    def one(x):
+        if before_step is not None:
+            before_step(orc.state)
+        return _step(c, orc, x)
     for call in T["calls"]:
-        steps = [_step(c, orc, call["x"][t]) for t in range(call["x"].shape[0])]
+        steps = [one(call["x"][t]) for t in range(call["x"].shape[0])]
         out.append(dict(v=np.stack([s[0] for s in steps]), s=np.stack([s[1] for s in steps]), pv=np.stack([s[2] for s in steps]),
                         eps0=orc.state[0].copy(), eps1=orc.state[1].copy(), arp=orc.state[2].copy()))
     return out

@@ -81,13 +81,14 @@ def conv_desc(c):
     from snn_modulation_classification_amd import ops
     d = ops.make_conv_desc(c["c_in"], c["c_out"], (c["h"], c["w"]), (c["kh"], c["kw"]), (c["pad_h"], c["pad_w"]),
                            (c["pool_h"], c["pool_w"]), c["target"], c["output_layer"], c["tau_tensor"],
-                           1.0 if c["refractory"] else 0.0, FZ.ALPHARP, c["stride"], c["dilation"], c["groups"])
+                           1.0 if c["refractory"] else 0.0, c.get("alpharp", FZ.ALPHARP), c["stride"], c["dilation"], c["groups"])
     assert ops.conv_out_shape(d) == FZ.conv_shape(c)
     return d
 
 
 def conv_forward(c, T, dev, off16=False, dequantised=False):
-    """The three steps of a case on the device -> (per-step dict of host copies, the last step's device tensors, kernel names)."""
+    """The steps of a case on the device (three; tests/value_cases.py draws up to eight) -> (per-step dict of host copies, the last
+    step's device tensors, kernel names)."""
     from snn_modulation_classification_amd import ops
     d = conv_desc(c)
     pooled = not (c["pool_h"] == 1 and c["pool_w"] == 1)
@@ -103,7 +104,7 @@ def conv_forward(c, T, dev, off16=False, dequantised=False):
         ro.update(out_W=cu(T["out_W"], dev), out_b=cu(T["out_b"], dev))
     steps, out = [], {}
     with ops.kernel_trace() as tr:
-        for t in range(FZ.STEPS):
+        for t in range(len(T["x"])):
             s, p, o, pv, v = ops.conv_lif_step(d, cu(T["x"][t], dev, off16), W, b, *tau, eps0, eps1, arp, out=out, q8=q8, **ro)
             h = lambda a: None if a is None else a.detach().cpu().numpy().copy()
             steps.append(dict(s=h(s), p=h(p), o=h(o), pv=h(pv), v=h(v), eps0=h(eps0), eps1=h(eps1), arp=h(arp),

@@ -36,7 +36,7 @@ def dev():
 def _desc(c):
     from snn_modulation_classification_amd import ops
     return ops.make_conv_desc(c["c_in"], c["c_out"], (c["h"], c["w"]), (c["kh"], c["kw"]), (c["pad_h"], c["pad_w"]),
-                              (c["pool_h"], c["pool_w"]), 0, False, c.get("tau_tensor", 0), 1.0 if c["refractory"] else 0.0, A.ALPHARP,
+                              (c["pool_h"], c["pool_w"]), 0, False, c.get("tau_tensor", 0), 1.0 if c["refractory"] else 0.0, c.get("alpharp", A.ALPHARP),
                               c["stride"], c["dilation"], c["groups"])
 
 
@@ -65,9 +65,12 @@ def _same(got, ref, axis, tag, zero_sign=False):
                                   "max |diff| %.3g" % float(np.abs(g - r).max())))
 
 
-def run_case(c, dev):
+def run_case(c, dev, run=None, count=True):
+    """every call of a case on the device against the oracle's trajectory -> host copies of every call's outputs and state.
+    run: (tensors, trajectory) of another draw of the same geometry (tests/value_cases.py), not counted as a case of this file"""
     from snn_modulation_classification_amd import ops
-    T_, traj = A.run(c)
+    T_, traj = A.run(c) if run is None else run
+    outs = []
     B = c["B"]
     ch, cw, ph, pw = A.out_shape(c)
     d = _desc(c)
@@ -99,8 +102,11 @@ def run_case(c, dev):
         _same(eps1, ref["eps1"], 0, tag + ("eps1",))
         if c["refractory"]:
             _same(arp, ref["arp"], 0, tag + ("arp",))
-    SERVED[A.variant(c)] += 1
-    RAN.add(c["id"])
+        outs.append([t.cpu().numpy().copy() for t in (spk, pv, v, eps0, eps1) + ((arp,) if c["refractory"] else ())])
+    if count:
+        SERVED[A.variant(c)] += 1
+        RAN.add(c["id"])
+    return outs
 
 
 # ---------------------------------------------------------------------------------------------- 1, 3, 4: the case list

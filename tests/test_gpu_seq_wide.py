@@ -32,9 +32,9 @@ def dev():
     return torch.device("cuda")
 
 
-def _operands(c, dev):
+def _operands(c, dev, run=None):
     """device tensors of a case: weights, bias, time constants, the initial state tiled to B samples"""
-    T_, traj = W.run(c)
+    T_, traj = W.run(c) if run is None else run
     B = c["B"]
     cu = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     op = dict(W=cu(T_["W"]), b=(cu(T_["b"]) if T_["b"] is not None else None), tau4=cu(np.stack(T_["tau"]).astype(np.float32)),
@@ -57,9 +57,12 @@ def _call(c, op, n, spk_in, entry="wide"):
     return out, list(tr.names)
 
 
-def run_case(c, dev):
+def run_case(c, dev, run=None, count=True):
+    """every call of a case on the device against the oracle's trajectory -> host copies of every call's outputs and state.
+    run: (tensors, trajectory) of another draw of the same geometry (tests/value_cases.py), not counted as a case of this file"""
     from snn_modulation_classification_amd import ops
-    op, calls, traj = _operands(c, dev)
+    op, calls, traj = _operands(c, dev, run)
+    outs = []
     B = c["B"]
     ch, cw, ph, pw = W.out_shape(c)
     for k, ((n, spk_in), ref) in enumerate(zip(calls, traj)):
@@ -78,8 +81,11 @@ def run_case(c, dev):
         G._same(op["eps1"], ref["eps1"], 0, tag + ("eps1",))
         if c["refractory"]:
             G._same(op["arp"], ref["arp"], 0, tag + ("arp",))
-    SERVED[W.variant(c)] += 1
-    RAN.add(c["id"])
+        outs.append([t.cpu().numpy().copy() for t in (spk, pv, v, op["eps0"], op["eps1"]) + ((op["arp"],) if c["refractory"] else ())])
+    if count:
+        SERVED[W.variant(c)] += 1
+        RAN.add(c["id"])
+    return outs
 
 
 # ---------------------------------------------------------------------------------------------- the case list
