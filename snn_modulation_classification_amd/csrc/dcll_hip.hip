@@ -1994,11 +1994,12 @@ __global__ __launch_bounds__(512) void k_lif_seq_c32rp(const uint32_t *__restric
 // Chain position w owns the image rows TP_ROW_A[w] and TP_ROW_B[w] for the whole sequence and walks the whole chain
 // bias -> (cp = 0..15, ky, kx, h) of both itself: no accumulator ever leaves its wave, there are no slots and no stage
 // barriers.  The border pairs have 11 live tap rows, the inner ones 14, and the two waves of a SIMD are two chain positions
-// apart, so every SIMD carries 25 tap rows = 2800 MFMAs per step pair.  The A fragment of (cp, ky, kx) serves both tiles where
-// ky is a tap row of both; it is streamed from a fragment-ordered copy of the weights ([cp][tap][lane], lane = (h, co):
-// one coalesced 256-byte load per fragment, L2-resident, made by k_c32d_wfrag in front of every launch), into the 7 x 7
-// registers of one channel pair: the fragments of (cp + 1, ky) are requested as soon as the MFMAs of (cp, ky) have issued,
-// six tap rows ahead.  The B fragment is one ds_read_b32 per MFMA, base + immediate, fetched one tap row ahead.
+// apart, so every SIMD carries 25 tap rows = 2800 MFMAs per step pair.  A channel pair is walked by SOURCE ROW (os_walk_ok
+// below): the B fragment of (source row s, kx) — base + immediate, fetched one source row ahead — is read once and serves
+// both tiles, as tap row s + 3 - row of each.  The A fragments are streamed from a fragment-ordered copy of the weights
+// ([cp][ky][lane][8], lane = (h, co): a tap row of a lane is one 16-byte and one 12-byte load, L2-resident, made by
+// k_c32d_wfrag in front of every launch) into the 7 tap-row registers of one channel pair: tap row ky of cp + 1 is requested
+// as soon as the last MFMA that reads it in cp has issued.
 //
 // Images: a channel is 16 rows of pitch 19 (3 shared columns of padding, no padding rows: padded tap rows are never
 // read).  Four images — "t" and "t+1" for each parity of the step pair.  In pair p every wave reads the images of parity
@@ -2013,14 +2014,14 @@ __global__ __launch_bounds__(512) void k_lif_seq_c32rp(const uint32_t *__restric
 // refractory update of t + 1 follows that of t in the same lane, on an arp register the wave keeps for the sequence.
 // pv / v leave as 64-byte row pieces, the spike masks (the compare results) are parked in the lanes of one register and
 // leave as 16-bit halves of the packed words.
-// os_schedule_ok() checks ownership, balance, the parity rule and the LDS budget at compile time.
+// os_schedule_ok() checks ownership, balance, the parity rule and the LDS budget at compile time, os_walk_ok() the walk.
 // ------------------------------------------------------------------------------------------------------------
 constexpr int TP_ROW_A[8] = {0, 1, 4, 6, 12, 13, 8, 10}, TP_ROW_B[8] = {3, 2, 5, 7, 15, 14, 9, 11};
 constexpr int OS_CHF = 16 * ROWF;                   // a channel: 16 rows, pixel (r, x) at r * 19 + x + 3
 constexpr int OS_IMG = 32 * OS_CHF + 3;             // ... + the right padding of the last row of channel 31
 constexpr int OS_IMGP = 9744;                       // pitch of the images: 16 mod 32, the two halves of a B fragment on disjoint banks
 constexpr int OS_LDS_FLOATS = 4 * OS_IMGP;          // image (parity q, step dt) at (2 q + dt) * OS_IMGP
-constexpr int OS_WFRAG_FLOATS = 16 * 49 * 64;       // the weights in fragment order [cp][tap][lane]
+constexpr int OS_WFRAG_FLOATS = 16 * 7 * 64 * 8;    // the weights in fragment order [cp][ky][lane][8]: 7 kx and a zero
 static_assert(OS_IMGP % 32 == 16 && OS_IMGP >= OS_IMG, "image pitch");
 static_assert(OS_LDS_FLOATS * sizeof(float) <= 160 * 1024, "k_lif_seq_c32d: four eps1 images in 160 KiB of LDS");
 constexpr bool os_tap(int r, int ky) { return r + ky - 3 >= 0 && r + ky - 3 <= 15; }     // is tap row ky of output row r in the image?
@@ -2067,14 +2068,57 @@ constexpr bool os_schedule_ok()
 }
 static_assert(os_schedule_ok(), "k_lif_seq_c32d: row ownership / SIMD balance / image parity");
 
-// the weights of a 32 -> 32 7x7 layer in the order k_lif_seq_c32d streams them: [cp][tap][lane], lane = 32 h + co holds
-// W[co][2 cp + h][tap] — through dcll_wsrc::at, so int8 weights dequantise to exactly the values load_wf_c32 produces
+// The walk of a channel pair, by SOURCE ROW: s = os_lo(w) .. os_hi(w), kx = 0..6.  The B fragment of (s, kx) is read once
+// and feeds tile A as tap row s + 3 - RA and tile B as tap row s + 3 - RB, each where that tap row exists: every tile still
+// sees (ky ascending, kx, h).  After the MFMAs of source row s the A fragments of the tap rows that have had their LAST use
+// in this channel pair are refetched for the next one: tile B's tap row, and tile A's where tile B never uses it.
+constexpr int os_lo(int w) { return TP_ROW_A[w] - 3 < 0 ? 0 : TP_ROW_A[w] - 3; }        // (TP_ROW_A[w] < TP_ROW_B[w])
+constexpr int os_hi(int w) { return TP_ROW_B[w] + 3 > 15 ? 15 : TP_ROW_B[w] + 3; }
+constexpr bool os_ky_ok(int ky) { return ky >= 0 && ky <= 6; }
+constexpr int os_kya(int w, int s) { return s + 3 - TP_ROW_A[w]; }                      // tap row of tile A at source row s (if os_ky_ok)
+constexpr int os_kyb(int w, int s) { return s + 3 - TP_ROW_B[w]; }
+constexpr bool os_refetch_b(int w, int s) { return os_ky_ok(os_kyb(w, s)); }
+constexpr bool os_refetch_a(int w, int s) { return os_ky_ok(os_kya(w, s)) && !os_tap(TP_ROW_B[w], os_kya(w, s)); }
+constexpr bool os_walk_ok()
+{
+    int total = 0;
+    for (int w = 0; w < 8; ++w) {
+        if (TP_ROW_A[w] >= TP_ROW_B[w] || os_lo(w) < 0 || os_hi(w) > 15) return false;
+        int lastA = -1, lastB = -1, seenA = 0, seenB = 0;       // tap rows visited so far, per tile
+        int last_use[7] = {-1, -1, -1, -1, -1, -1, -1}, refetched[7] = {-1, -1, -1, -1, -1, -1, -1};
+        for (int s = os_lo(w); s <= os_hi(w); ++s) {
+            const int ka = os_kya(w, s), kb = os_kyb(w, s);
+            if (!os_ky_ok(ka) && !os_ky_ok(kb)) return false;   // no idle source row
+            if (os_ky_ok(ka)) {
+                if (!os_tap(TP_ROW_A[w], ka) || ka <= lastA) return false;     // never a padded one, ascending
+                lastA = ka; seenA |= 1 << ka; last_use[ka] = s; ++total;
+            }
+            if (os_ky_ok(kb)) {
+                if (!os_tap(TP_ROW_B[w], kb) || kb <= lastB) return false;
+                lastB = kb; seenB |= 1 << kb; last_use[kb] = s; ++total;
+            }
+            if (os_refetch_b(w, s)) { if (refetched[kb] >= 0) return false; refetched[kb] = s; }
+            if (os_refetch_a(w, s)) { if (refetched[ka] >= 0) return false; refetched[ka] = s; }
+        }
+        for (int ky = 0; ky < 7; ++ky) {
+            if (((seenA >> ky) & 1) != (os_tap(TP_ROW_A[w], ky) ? 1 : 0)) return false;     // every live one exactly once
+            if (((seenB >> ky) & 1) != (os_tap(TP_ROW_B[w], ky) ? 1 : 0)) return false;
+            if (refetched[ky] != last_use[ky]) return false;    // an A row is reloaded right after its last use, an unused one never
+        }
+    }
+    return total == 100;
+}
+static_assert(os_walk_ok(), "k_lif_seq_c32d: the source-row walk visits the 100 live (row, tap row) combinations once, in order");
+
+// the weights of a 32 -> 32 7x7 layer in the order k_lif_seq_c32d streams them: [cp][ky][lane][8], lane = 32 h + co holds
+// W[co][2 cp + h][ky][0..6] and a zero (never multiplied): a tap row of a lane is one 16-byte and one 12-byte load —
+// through dcll_wsrc::at, so int8 weights dequantise to exactly the values load_wf_c32 produces
 __global__ __launch_bounds__(256) void k_c32d_wfrag(const dcll_wsrc W, float *__restrict__ wfrag)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= OS_WFRAG_FLOATS) return;
-    const int lane = i & 63, f = i >> 6, tap = f % 49, cp = f / 49, co = lane & 31, h = lane >> 5;
-    wfrag[i] = W.at(((long)co * 32 + 2 * cp + h) * 49 + tap, co);
+    const int kx = i & 7, lane = (i >> 3) & 63, f = i >> 9, ky = f % 7, cp = f / 7, co = lane & 31, h = lane >> 5;
+    wfrag[i] = kx < 7 ? W.at(((long)co * 32 + 2 * cp + h) * 49 + ky * 7 + kx, co) : 0.0f;
 }
 
 template <bool REFRACTORY, int OUT>     // OUT bit0: pv, bit1: v
@@ -2103,8 +2147,8 @@ __global__ __launch_bounds__(512) void k_lif_seq_c32d(const uint32_t *__restrict
     // everything below knows its chain position at compile time: one copy per wave of the workgroup
     auto run = [&](auto WC) {
         constexpr int W = decltype(WC)::value, RA = TP_ROW_A[W], RB = TP_ROW_B[W], NKY = os_nky(W);
-        constexpr int LO = RA - 3 < 0 ? 0 : RA - 3;             // first source row of the wave (RA < RB)
-        static_assert(RA < RB && ((RB + 3 > 15 ? 15 : RB + 3) - LO) * ROWF + 6 < 256, "B-fragment offsets within ds_read2_b32's range");
+        constexpr int LO = os_lo(W), NS = os_hi(W) - LO + 1;    // first source row of the wave (RA < RB), source rows
+        static_assert(RA < RB && (NS - 1) * ROWF + 6 < 256, "B-fragment offsets within ds_read2_b32's range");
         constexpr bool FIRST = os_trace_first(W);
         // traces of my channels 4W..4W+3: register group (m, e) = channel 4W + 2e + h, image row 2m + rb, pixel px
         float e0[8][2], e1[8][2];
@@ -2170,7 +2214,6 @@ __global__ __launch_bounds__(512) void k_lif_seq_c32d(const uint32_t *__restrict
         const unsigned soff = (unsigned)((lane >> 1) & 1) * ((unsigned)B * 1024u) +
                               32u * (2 * ((lane >> 2) & 1) + 8 * ((lane >> 3) & 3) + 4 * (lane & 1));
         const auto wrs = tile_rsrc(wfrag);
-        const unsigned wlane = 4u * lane;
         const f32x4 *bvp = (const f32x4 *)(sbias + 16 * h);
 
         // refractory traces of my two rows: register m = channel 2 (m & 1) + 8 (m >> 1) + 4 h + rb, pixel px
@@ -2181,14 +2224,21 @@ __global__ __launch_bounds__(512) void k_lif_seq_c32d(const uint32_t *__restrict
             arpA[m] = REFRACTORY ? arp_g[aidx + RA * 16] : 0.0f;
             arpB[m] = REFRACTORY ? arp_g[aidx + RB * 16] : 0.0f;
         }
-        // A fragments of one channel pair; those of cp = 0 now, then always one channel pair ahead
-        float wb[7][7];
-        static_for<0, NKY>([&](auto IC) {
-            constexpr int KY = os_ky(W, decltype(IC)::value);
-#pragma unroll
-            for (int kx = 0; kx < 7; ++kx)
-                wb[KY][kx] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(wrs, wlane, (KY * 7 + kx) * 256, 0));
-        });
+        // A fragments of one channel pair; those of cp = 0 now, then always one channel pair ahead.  A tap row of a lane is
+        // 8 contiguous floats of the streamed copy (7 kx and a zero that is never loaded): one dwordx4 + one dwordx3
+        f32x4 wq[7];
+        f32x3 wr[7];
+        const unsigned wlane = 32u * lane;
+        auto load_a = [&](auto KYC, const unsigned wo) {
+            constexpr int KY = decltype(KYC)::value;
+            wq[KY] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrs, wlane, wo + KY * 2048u, 0));
+            wr[KY] = __builtin_bit_cast(f32x3, __builtin_amdgcn_raw_buffer_load_b96(wrs, wlane + 16u, wo + KY * 2048u, 0));
+        };
+        auto wa = [&](auto KYC, auto KXC) -> float {
+            constexpr int KY = decltype(KYC)::value, KX = decltype(KXC)::value;
+            if constexpr (KX < 4) return wq[KY][KX]; else return wr[KY][KX - 4];
+        };
+        static_for<0, NKY>([&](auto IC) { load_a(std::integral_constant<int, os_ky(W, decltype(IC)::value)>{}, 0u); });
         if (FIRST && NP > 1) load_masks(2);
         lds_barrier();          // steps 0, 1 of every channel are in the images of parity 0
 
@@ -2208,42 +2258,44 @@ __global__ __launch_bounds__(512) void k_lif_seq_c32d(const uint32_t *__restrict
                 accA[4 * c + 0] = q[0]; accA[4 * c + 1] = q[1]; accA[4 * c + 2] = q[2]; accA[4 * c + 3] = q[3];
             }
             accB = accA;
-            float bqA[2][7], bqB[2][7];
-            auto fetch_b = [&](auto SETC, auto KYC, lds_cfloat *base) {
-                constexpr int SET = decltype(SETC)::value, KY = decltype(KYC)::value;
+            // by source row (os_walk_ok): ONE B register set per source row serves both tiles, fetched one row ahead
+            float bq[2][7];
+            auto fetch_b = [&](auto SETC, auto SC, lds_cfloat *base) {
+                constexpr int SET = decltype(SETC)::value, S = decltype(SC)::value;
 #pragma unroll
-                for (int kx = 0; kx < 7; ++kx) {
-                    if (os_tap(RA, KY)) bqA[SET][kx] = base[(RA + KY - 3 - LO) * ROWF + kx];
-                    if (os_tap(RB, KY)) bqB[SET][kx] = base[(RB + KY - 3 - LO) * ROWF + kx];
-                }
+                for (int kx = 0; kx < 7; ++kx) bq[SET][kx] = base[(S - LO) * ROWF + kx];
             };
-            fetch_b(std::integral_constant<int, 0>{}, std::integral_constant<int, os_ky(W, 0)>{}, ib0);
+            fetch_b(std::integral_constant<int, 0>{}, std::integral_constant<int, LO>{}, ib0);
 #pragma nounroll
             for (int c2 = 0; c2 < 8; ++c2) {
-                const unsigned wnext0 = (unsigned)(2 * c2 + 1) * (49u * 256u), wnext1 = (unsigned)((2 * c2 + 2) & 15) * (49u * 256u);
-                static_for<0, 2 * NKY>([&](auto RC) {
-                    constexpr int R = decltype(RC)::value, CPO = R / NKY, KY = os_ky(W, R % NKY);
-                    if constexpr (R + 1 == NKY) {           // the even channel pair has been fetched: on to the next iteration's
+                const unsigned wnext0 = (unsigned)(2 * c2 + 1) * (7u * 2048u), wnext1 = (unsigned)((2 * c2 + 2) & 15) * (7u * 2048u);
+                static_for<0, 2 * NS>([&](auto RC) {
+                    constexpr int R = decltype(RC)::value, CPO = R / NS, S = LO + R % NS;
+                    constexpr bool LA = os_ky_ok(os_kya(W, S)), LB = os_ky_ok(os_kyb(W, S));
+                    constexpr int KYA = LA ? os_kya(W, S) : 0, KYB = LB ? os_kyb(W, S) : 0;
+                    if constexpr (R + 1 == NS) {            // the even channel pair has been fetched: on to the next iteration's
                         ib0 += 4 * OS_CHF;
                         asm volatile("" : "+v"(ib0));
                     }
-                    if constexpr (R + 1 < 2 * NKY)
-                        fetch_b(std::integral_constant<int, (R + 1) & 1>{}, std::integral_constant<int, os_ky(W, (R + 1) % NKY)>{},
-                                (R + 1) / NKY ? ib1 : ib0);
+                    if constexpr (R + 1 < 2 * NS)
+                        fetch_b(std::integral_constant<int, (R + 1) & 1>{}, std::integral_constant<int, LO + (R + 1) % NS>{},
+                                (R + 1) / NS ? ib1 : ib0);
                     else if (c2 < 7)
-                        fetch_b(std::integral_constant<int, 0>{}, std::integral_constant<int, os_ky(W, 0)>{}, ib0);
+                        fetch_b(std::integral_constant<int, 0>{}, std::integral_constant<int, LO>{}, ib0);
                     __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int kx = 0; kx < 7; ++kx) {
-                        if (os_tap(RA, KY)) accA = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[KY][kx], bqA[R & 1][kx], accA, 0, 0, 0);
-                        if (os_tap(RB, KY)) accB = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[KY][kx], bqB[R & 1][kx], accB, 0, 0, 0);
-                    }
+                    static_for<0, 7>([&](auto KXC) {
+                        constexpr int KX = decltype(KXC)::value;
+                        if constexpr (LA)
+                            accA = __builtin_amdgcn_mfma_f32_32x32x2f32(wa(std::integral_constant<int, KYA>{}, KXC), bq[R & 1][KX], accA, 0, 0, 0);
+                        if constexpr (LB)
+                            accB = __builtin_amdgcn_mfma_f32_32x32x2f32(wa(std::integral_constant<int, KYB>{}, KXC), bq[R & 1][KX], accB, 0, 0, 0);
+                    });
                     __builtin_amdgcn_sched_barrier(0);
-                    // this tap row of the next channel pair (after cp = 15: of cp = 0, for the next step pair)
+                    // the tap rows that had their last use: those of the next channel pair (after cp = 15: of cp = 0, for
+                    // the next step pair)
                     const unsigned wo = CPO ? wnext1 : wnext0;
-#pragma unroll
-                    for (int kx = 0; kx < 7; ++kx)
-                        wb[KY][kx] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(wrs, wlane, wo + (KY * 7 + kx) * 256, 0));
+                    if constexpr (os_refetch_b(W, S)) load_a(std::integral_constant<int, KYB>{}, wo);
+                    if constexpr (os_refetch_a(W, S)) load_a(std::integral_constant<int, KYA>{}, wo);
                     __builtin_amdgcn_sched_barrier(0);
                 });
                 ib1 += 4 * OS_CHF;
@@ -4062,7 +4114,7 @@ static void launch_c32(int out, int B, hipStream_t st, const uint32_t *spk_in, d
 
 // Workspace of k_lif_seq_c32d: the fragment-ordered weights of the call in flight, ONE BUFFER PER (device, stream).  Calls on
 // one stream run in order, so the helper of the next call overwrites the copy only after the previous kernel has finished;
-// calls on different streams never share a buffer.  Buffers live as long as the library (200 704 bytes each).  A capturing
+// calls on different streams never share a buffer.  Buffers live as long as the library (229 376 bytes each).  A capturing
 // stream refuses hipMalloc in the default capture mode, so the first call on it allocates in relaxed mode.
 static int c32d_workspace(hipStream_t st, float **out)
 {
