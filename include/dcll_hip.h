@@ -592,6 +592,39 @@ int dcll_conv_lif_backward_any_open(const dcll_conv_desc *d, const float *eps1, 
                                     const float **part, int32_t *nchunk, void *stream);
 
 /*
+ * Added under ABI 10 (DCLL_ABI_VERSION is unchanged: a caller detects these three symbols by symbol lookup) — the calls above for
+ * the layers of 33 .. 64 output channels that a --netscale above 1 makes (k_bwd_wgrad_wide, csrc/dcll_bwd_wide.hip): arguments,
+ * results and scratch rule of dcll_conv_lif_backward_any / _any_open (scratch_floats >= B c_out ch cw + k (c_out (c_in kh kw + 1)),
+ * k >= 1 partial rows, at most 256 are used; less: DCLL_ERR_INVALID).  Additions only: the default dispatch, the _any calls, their
+ * launch logs and refusals (dcll_conv_lif_backward_any's "c_out <= 32" included) are unchanged; dv, the fixed-order reduction
+ * and the output_ gradient are the same kernels.
+ * Served (else DCLL_ERR_UNSUPPORTED, before any launch): stride = dilation = groups = 1; any c_in; c_out <= 64; kh, kw <= 16; any
+ * padding, pooling and batch; and a smallest working set within the 160 KiB of LDS of a workgroup: the formula above, 4 bytes x
+ * (cg (h + 2 pad_h)(w + 2 pad_w) + 1 + c_out (ch (cw rounded up to even) | 1)).
+ * c_out <= 32: the call IS dcll_conv_lif_backward_any[_open] — same kernels, launch log, bits, refusals (with that call's name
+ * in the message) and _lds value — so a network of mixed widths goes through one entry point.
+ * c_out 33 .. 64: k_bwd_wgrad_any's decomposition with M = c_out padded to 64 rows, two 32-row tiles: a wave runs both M tiles
+ * of its column tiles, one LDS read of the B operand feeding two MFMAs (rows at or beyond c_out read the last real row and are
+ * not stored).  Column split, pixel split (its pieces added in wave order), the 256-chunk limit, the odd-cw rule and the
+ * small-batch lowering (never more LDS than the full launch) are those of the _any call.  The launch log names the form, NQ =
+ * column tiles per wave (1, 2, 4; 2 NQ accumulator tiles): "k_bwd_wgrad_wide<NQ>", "k_bwd_wgrad_wide<NQ> (column split)",
+ * "k_bwd_wgrad_wide<1> (pixel split)" or "k_bwd_wgrad_wide<1> (column split, pixel split)".
+ * Every sum has a fixed order: two runs give the same bits, and _wide_open + dcll_grad_reduce_adam gives _wide's bits.  Not
+ * bit-identical to dcll_conv_lif_backward (another order).
+ * dcll_conv_lif_backward_wide_lds returns the LDS bytes per workgroup of a full launch (no launch uses more; c_out <= 32:
+ * dcll_conv_lif_backward_any_lds), or 0 for a descriptor that is not served (invalid ones included).
+ */
+int64_t dcll_conv_lif_backward_wide_lds(const dcll_conv_desc *d);
+int dcll_conv_lif_backward_wide(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                                const float *g_p, const float *g_o, const float *g_pv, const float *g_v, const float *i2o_W,
+                                float *dW, float *db, float *d_outW, float *d_outb, float *scratch, int64_t scratch_floats,
+                                int32_t B, void *stream);
+int dcll_conv_lif_backward_wide_open(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                                     const float *g_p, const float *g_o, const float *g_pv, const float *g_v, const float *i2o_W,
+                                     float *d_outW, float *d_outb, float *scratch, int64_t scratch_floats, int32_t B,
+                                     const float **part, int32_t *nchunk, void *stream);
+
+/*
  * ABI 10 — one layer step of ANY plain conv layer in one MFMA launch (k_lif_step_any): dcll_conv_lif_step with the same arguments
  * and results for the layers that call serves with k_trace + k_conv_lif[_tiled] + k_pool.  Additions only: dcll_conv_lif_step, its
  * dispatch, launch logs and refusals are unchanged.  Differences to dcll_conv_lif_step:

@@ -152,6 +152,9 @@ SIGNATURES = {
     "dcll_conv_lif_backward_any_lds": (_I64, [_DP]),
     "dcll_conv_lif_backward_any": (_I32, [_DP] + [_P] * 13 + [_I64, _I32, _P]),
     "dcll_conv_lif_backward_any_open": (_I32, [_DP] + [_P] * 11 + [_I64, _I32, ctypes.POINTER(ctypes.c_void_p), _IP, _P]),
+    "dcll_conv_lif_backward_wide_lds": (_I64, [_DP]),
+    "dcll_conv_lif_backward_wide": (_I32, [_DP] + [_P] * 13 + [_I64, _I32, _P]),
+    "dcll_conv_lif_backward_wide_open": (_I32, [_DP] + [_P] * 11 + [_I64, _I32, ctypes.POINTER(ctypes.c_void_p), _IP, _P]),
     "dcll_conv_lif_step_any_lds": (_I64, [_DP]),
     "dcll_conv_lif_step_any_scratch": (_I64, [_DP]),
     "dcll_conv_lif_step_any": (_I32, [_DP] + [_P] * 20 + [_I32, _P]),

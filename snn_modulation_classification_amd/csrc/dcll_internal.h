@@ -157,6 +157,14 @@ __attribute__((visibility("hidden")))
 int dcll_launch_bwd_wgrad_any(const dcll_conv_desc *d, const float *gvf, const float *eps1, float *part, int32_t B,
                               long *nchunk, hipStream_t st);
 
+// k_bwd_wgrad_wide (dcll_bwd_wide.hip): MFMA weight gradient of a plain conv layer with 33 .. 64 output channels (kernel up to
+// 16x16), two 32-row M tiles per wave.  _check and launcher as for k_bwd_wgrad_any; layers of at most 32 output channels never
+// reach them (dcll_conv_lif_backward_wide hands those to the _any path)
+__attribute__((visibility("hidden"))) int dcll_bwd_wgrad_wide_check(const dcll_conv_desc *d, const char *who);
+__attribute__((visibility("hidden")))
+int dcll_launch_bwd_wgrad_wide(const dcll_conv_desc *d, const float *gvf, const float *eps1, float *part, int32_t B,
+                               long *nchunk, hipStream_t st);
+
 // k_seq_any_wprep (dcll_seq_any.hip): the weights of a plain conv layer in MFMA fragment order, 64 floats per chain step
 // (_steps: (c_in / 2) kh kw + (c_in odd: (kh kw + 1) / 2)) — shared by k_lif_seq_any and k_lif_step_any
 __attribute__((visibility("hidden"))) long dcll_seq_any_steps(const dcll_conv_desc *d);

@@ -1169,6 +1169,8 @@ class DCLLBase(nn.Module):
     # -- the MFMA weight gradient of any plain conv layer (k_bwd_wgrad_any, ABI 9): opt-in, beside the default dispatch ------
     any_learning_path = False       # _learn_tail: dcll_conv_lif_backward_any[_open] instead of dcll_conv_lif_backward[_open]
 
+    wide_learning_path = False      # _learn_tail: dcll_conv_lif_backward_wide[_open] (k_bwd_wgrad_wide: layers of up to 64 channels)
+
     w3_learning_path = False        # _learn_tail: dcll_conv_lif_backward_w3[_open] (k_bwd_wgrad_w3); set by ConvNetwork.w3_step_path
     w3_first_wgrad = False          # with w3_learning_path: dcll_conv_lif_backward_w3f[_open] (the c_in 1 layer on k_bwd_wgrad_w3f);
                                     # set by ConvNetwork.w3_first_wgrad
@@ -1190,6 +1192,14 @@ class DCLLBase(nn.Module):
             return False
         return ops.backward_any_supported(L.i2h.make_desc(L.im_dims, L.pooling, L.i2o.weight.shape[0], L.output_layer))
 
+    def backward_wide_supported(self):
+        """True if this slice's native learning step can take its weight gradient from dcll_conv_lif_backward_wide: as
+        backward_any_supported with up to 64 output channels (ops.backward_wide_supported; c_out <= 32 runs k_bwd_wgrad_any)."""
+        L = self.dclllayer
+        if not isinstance(L, Conv2dDCLLlayer) or L.i2h._general():
+            return False
+        return ops.backward_wide_supported(L.i2h.make_desc(L.im_dims, L.pooling, L.i2o.weight.shape[0], L.output_layer))
+
     def step_any_supported(self):
         """True if this slice's layer steps can run on k_lif_step_any (Conv2dDCLLlayer.step_any_supported)."""
         L = self.dclllayer
@@ -1206,7 +1216,7 @@ class DCLLBase(nn.Module):
         dcll_conv_lif_backward into the parameters' .grad.  `open_reduce`: the weight gradient's last reduction is left to
         the caller's ops.grad_reduce_adam (self._learn_bufs['grads']['parts']); `defer_backward` (a list, with open_reduce): the
         backward is not launched here but appended for ops.conv_lif_backward_open_multi (all slices' dv in one launch) — with
-        any_learning_path or w3_learning_path the slice's own open call is launched at once instead.
+        any_learning_path, wide_learning_path or w3_learning_path the slice's own open call is launched at once instead.
         -> loss (1,) device tensor or None"""
         L = self.dclllayer
         i2h = L.i2h
@@ -1240,7 +1250,8 @@ class DCLLBase(nn.Module):
             ops.conv_lif_backward(desc, i2h.state.eps1, v, pv, g_p, g_o, None, None, L.i2o.weight,
                                   want_out=L.output_layer, out=gb, open_reduce=open_reduce,
                                   defer=defer_backward if open_reduce else None, any_path=self.any_learning_path,
-                                  w3_path=self.w3_learning_path, w3_first=self.w3_first_wgrad, w3_dv=self.w3_dv)
+                                  w3_path=self.w3_learning_path, w3_first=self.w3_first_wgrad, w3_dv=self.w3_dv,
+                                  wide_path=self.wide_learning_path)
         return loss
 
     def _grads_into_slab(self):

@@ -306,6 +306,7 @@ class ConvNetwork(torch.nn.Module):
                                            L.i2o.bias)]
             walk(s.__dict__.get('_learn_bufs', {}))
             sig.append(bool(s.any_learning_path))
+            sig.append(bool(s.wide_learning_path))
             sig.append(bool(L.i2h.any_step_path))
             sig.append((bool(s.w3_learning_path), bool(L.i2h.w3_step_path), bool(s.w3_first_wgrad), bool(s.w3_dv)))
             for t in s._adam_tensors(advance=False):
@@ -881,10 +882,36 @@ class ConvNetwork(torch.nn.Module):
         on = bool(on)
         if on and self.w3_step_path:
             raise ops._lib.DCLLUnsupported('any_learning_path cannot be combined with w3_step_path')
+        if on and any(s.wide_learning_path for s in self.dcll_slices):
+            raise ops._lib.DCLLUnsupported('any_learning_path cannot be combined with wide_learning_path')
         if on and not self.backward_any_supported():
             raise ops._lib.DCLLUnsupported('dcll_conv_lif_backward_any does not serve every layer of this network')
         for s in self.dcll_slices:
             s.any_learning_path = on            # (part of _graph_signature: a captured timestep of the other path is retaken)
+
+    # -- the MFMA weight gradient of layers with up to 64 output channels (k_bwd_wgrad_wide): opt-in, beside the default dispatch --
+    def backward_wide_supported(self):
+        """True if every slice is served by dcll_conv_lif_backward_wide (DCLLBase.backward_wide_supported)."""
+        return all(s.backward_wide_supported() for s in self.dcll_slices)
+
+    @property
+    def wide_learning_path(self):
+        """True: every slice's learning step takes its weight gradient from dcll_conv_lif_backward_wide — k_bwd_wgrad_wide (fp32
+        MFMA, two 32-row M tiles) for the layers of 33 .. 64 output channels that a netscale above 1 makes, k_bwd_wgrad_any for
+        the narrower ones — instead of the default dispatch.  The step's structure is unchanged: layer kernels, tails, one
+        dcll_grad_reduce_adam.  Default False; setting it on a network that is not fully served, or together with w3_step_path or
+        any_learning_path, raises DCLLUnsupported and leaves it off; switching it off is always allowed."""
+        return all(s.wide_learning_path for s in self.dcll_slices)
+
+    @wide_learning_path.setter
+    def wide_learning_path(self, on):
+        on = bool(on)
+        if on and (self.w3_step_path or any(s.any_learning_path for s in self.dcll_slices)):
+            raise ops._lib.DCLLUnsupported('wide_learning_path cannot be combined with w3_step_path / any_learning_path')
+        if on and not self.backward_wide_supported():
+            raise ops._lib.DCLLUnsupported('dcll_conv_lif_backward_wide does not serve every layer of this network')
+        for s in self.dcll_slices:
+            s.wide_learning_path = on           # (part of _graph_signature: a captured timestep of the other path is retaken)
 
     # -- the MFMA per-step forward of any plain conv layer (k_lif_step_any, ABI 10): opt-in, beside the default dispatch -------
     def step_any_supported(self):
@@ -934,6 +961,8 @@ class ConvNetwork(torch.nn.Module):
         if on and (any(s.any_learning_path for s in self.dcll_slices) or
                    any(s.dclllayer.i2h.any_step_path for s in self.dcll_slices)):
             raise ops._lib.DCLLUnsupported('w3_step_path cannot be combined with any_step_path / any_learning_path')
+        if on and any(s.wide_learning_path for s in self.dcll_slices):
+            raise ops._lib.DCLLUnsupported('w3_step_path cannot be combined with wide_learning_path')
         if on and not self.w3_step_supported():
             raise ops._lib.DCLLUnsupported('dcll_conv_lif_step_w3 / dcll_conv_lif_backward_w3 do not serve every layer of this '
                                            'network')

@@ -265,13 +265,25 @@ def backward_any_supported(desc):
     return backward_any_lds(desc) > 0
 
 
+def backward_wide_lds(desc):
+    """LDS bytes per workgroup of k_bwd_wgrad_wide on this layer (c_out <= 32: of k_bwd_wgrad_any, which serves it), 0 = the layer is
+    not served (dcll_conv_lif_backward_wide_lds)."""
+    return int(_lib.get().dcll_conv_lif_backward_wide_lds(ctypes.byref(desc)))
+
+
+def backward_wide_supported(desc):
+    """True if conv_lif_backward(wide_path=True) serves the layer: a plain conv with c_out <= 64, a kernel up to 16x16 and a
+    smallest working set (one column tile's padded eps1 channels + the sample's dv plane) within the 160 KiB of LDS."""
+    return backward_wide_lds(desc) > 0
+
+
 BWD_ANY_MAX_CHUNKS = 256        # batch chunks (partial rows) of k_bwd_wgrad_any, at most
 BWD_W3F_PB = 128                # pixels of a job of k_bwd_wgrad_w3f (the flattened B x h w stream): at most one partial row per job
 W3_FIRST_WGRAD, W3_DV = 1, 2    # flag bits of dcll_conv_lif_backward_w3_ex[_open] (DCLL_W3_FIRST_WGRAD, DCLL_W3_DV)
 
 
 def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want_out, out=None, open_reduce=False, defer=None,
-                      any_path=False, w3_path=False, w3_first=False, w3_dv=False):
+                      any_path=False, w3_path=False, w3_first=False, w3_dv=False, wide_path=False):
     """Gradients of one layer step (dcll_conv_lif_backward) -> (dW, db, d_outW, d_outb).  `out`: optional dict with
     preallocated 'dW', 'db', 'd_outW', 'd_outb', 'bwd_scratch' (the learning loop writes into the parameters' .grad).
     `open_reduce`: dcll_conv_lif_backward_open — dW / db are NOT written yet; the partial rows of the weight gradient stay
@@ -286,7 +298,12 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
     (c_in 1) takes its weight gradient from k_bwd_wgrad_w3f (a streaming reduction) instead of the generic k_bwd_wgrad.
     `w3_dv` (with `w3_path`; alone it raises; independent of `w3_first`): dcll_conv_lif_backward_w3_ex[_open] with DCLL_W3_DV — the
     dv plane from k_bwd_dv_w3 instead of k_bwd_dv, bit for bit the same plane (a layer with more than 32 readout rows keeps
-    k_bwd_dv); the scratch size is unchanged."""
+    k_bwd_dv); the scratch size is unchanged.
+    `wide_path`: dcll_conv_lif_backward_wide[_open] — the weight gradient of a plain conv layer with up to 64 output channels on
+    k_bwd_wgrad_wide (fp32 MFMA, two 32-row M tiles; backward_wide_supported); a layer with c_out <= 32 runs the `any_path` kernels,
+    same bits and launch log.  `defer` as for `any_path`; combined with `any_path` or `w3_path` it raises."""
+    if wide_path and (any_path or w3_path):
+        raise ValueError("conv_lif_backward(wide_path=True) cannot be combined with any_path=True or w3_path=True")
     if w3_path and any_path:
         raise ValueError("conv_lif_backward(w3_path=True) cannot be combined with any_path=True")
     if w3_first and not w3_path:
@@ -316,7 +333,7 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
     jobs = B * max(1, (desc.h // 16) * (desc.w // 16))
     per_chunk = desc.c_out * ((desc.c_in // desc.groups) * desc.kh * desc.kw + 1)
     nchunk = min(jobs, 1024 if desc.c_in == 1 else 256)      # (first layer: 128-thread workgroups, 6 KB partial rows)
-    if any_path:
+    if any_path or wide_path:
         nchunk = min(B, BWD_ANY_MAX_CHUNKS)
     if w3_path and desc.c_in == 64:
         nchunk = min(-(-B * desc.h * desc.w // 128), BWD_ANY_MAX_CHUNKS)       # (k_bwd_wgrad_w3: one row per 128-pixel block)
@@ -337,10 +354,12 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
     # gradients in one call would then alias)
     gp_, go_, gpv_, gv_ = c(g_p), (c(g_o) if want_out else None), c(g_pv), c(g_v)
     fn = "dcll_conv_lif_backward_w3f" if w3_first else "dcll_conv_lif_backward_w3" if w3_path else "dcll_conv_lif_backward_any" if any_path else "dcll_conv_lif_backward"
+    if wide_path:
+        fn = "dcll_conv_lif_backward_wide"
     flags = ()
     if w3_dv:       # (the flag-word entry points; without w3_dv the calls above are made as before)
         fn, flags = "dcll_conv_lif_backward_w3_ex", (W3_DV | (W3_FIRST_WGRAD if w3_first else 0),)
-    if defer is not None and not any_path and not w3_path:       # (open form, launched later with other layers': conv_lif_backward_open_multi)
+    if defer is not None and not any_path and not w3_path and not wide_path:       # (open form, launched later with other layers': conv_lif_backward_open_multi)
         item = _lib.BwdItem(ctypes.pointer(desc), ptr(eps1), ptr(v), ptr(pv_pooled), ptr(gp_), ptr(go_), ptr(gpv_), ptr(gv_),
                             ptr(i2o_W), ptr(d_outW), ptr(d_outb), ptr(scratch), n_scratch, B, 0, None, 0, 0)
         defer.append(dict(item=item, out=out, desc=desc, dW=dW, db=db, scratch=scratch,

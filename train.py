@@ -93,6 +93,17 @@ def parse_args(argv=None):
                         'plain conv layer with c_out <= 32 and a kernel up to 16x16, which lifts the default path\'s 64-tap '
                         'limit) where ConvNetwork.backward_any_supported() holds; ignored with a notice elsewhere.  Whether it '
                         'is faster than the default dispatch is not measured yet (DESIGN 4.2a; experiments/bwd_any_timing.py)')
+    p.add_argument('--wide_learning_path', action='store_true',
+                   help='opt in: every layer\'s weight gradient of the learning step runs through dcll_conv_lif_backward_wide — '
+                        'k_bwd_wgrad_wide (fp32 MFMA, two 32-row M tiles per wave) for layers of 33-64 output channels (--netscale up '
+                        'to 2), k_bwd_wgrad_any up to 32 — where ConvNetwork.backward_wide_supported() holds; ignored with a notice '
+                        'elsewhere and together with --any_learning_path / --w3_step_path.  Measured on an MI355X against the same tree '
+                        'without the flag, five alternating fresh processes, min-max ms per net.learn timestep: radio_ml_conv.yaml at '
+                        'netscale 2 on 16x16, T = 128: 7.035-7.072 -> 0.752-0.757 at B = 64 (9.3-9.4x), 19.03-19.16 -> 4.049-4.071 at '
+                        'B = 512 (4.7x); mnist_conv.yaml at netscale 2, T = 50: 2.178-2.193 -> 0.441-0.444 at B = 32 (4.9-5.0x), '
+                        '10.51-10.55 -> 2.411-2.423 at B = 512 (4.3-4.4x); every layer\'s open backward call is faster, none slower; '
+                        'the per-step forward of such layers stays on the default kernels (DESIGN 4.2d; '
+                        'profiles/r20_bwd_wide_timing.txt; experiments/bwd_wide_timing.py)')
     p.add_argument('--any_step_path', action='store_true',
                    help='opt in: every per-step layer call (net.test per timestep, every learning timestep) runs k_lif_step_any '
                         '(one fp32-MFMA launch with the traces and the pooling fused in; any plain conv layer with c_out <= 32 and '
@@ -187,6 +198,7 @@ def main(argv=None):
     _opt_in_any_learning(net, args)
     _opt_in_any_step(net, args)
     _opt_in_w3_step(net, args)
+    _opt_in_wide_learning(net, args)
     parallel.freeze_startup_heap()          # (a full GC pass over the start-up heap costs ~100 ms inside the T-loop)
 
     if not args.no_save:
@@ -363,6 +375,19 @@ def _opt_in_any_learning(net, args):
         print('--any_learning_path ignored: k_bwd_wgrad_any does not serve every layer of this network')
 
 
+def _opt_in_wide_learning(net, args):
+    """--wide_learning_path: switch the network's learning step to dcll_conv_lif_backward_wide (k_bwd_wgrad_wide for layers of 33-64
+    output channels, k_bwd_wgrad_any below) where every slice is served and no other learning path is in effect."""
+    if not getattr(args, 'wide_learning_path', False):
+        return
+    if net.any_learning_path or net.w3_step_path:
+        print('--wide_learning_path ignored: another learning path (--any_learning_path / --w3_step_path) is in effect')
+    elif net.backward_wide_supported():
+        net.wide_learning_path = True
+    else:
+        print('--wide_learning_path ignored: dcll_conv_lif_backward_wide does not serve every layer of this network')
+
+
 def _opt_in_any_step(net, args):
     """--any_step_path: switch the network's per-step layer calls to k_lif_step_any where every layer is served."""
     if not args.any_step_path:
@@ -424,6 +449,7 @@ def main_mnist(args):
     _opt_in_any_learning(net, args)
     _opt_in_any_step(net, args)
     _opt_in_w3_step(net, args)
+    _opt_in_wide_learning(net, args)
     use_wide = _opt_in_wide_sequence(net, args, net.sequence_supported())      # (the condition of --any_sequence_path below)
     parallel.freeze_startup_heap()          # (a full GC pass over the start-up heap costs ~100 ms inside the T-loop)
     n_test = int(np.ceil(float(args.n_test_samples) / args.batch_size_test))
