@@ -665,6 +665,40 @@ int dcll_conv_lif_step_any(const dcll_conv_desc *d, const float *x, const float 
                            float *out_p, float *out_o, float *out_pv, float *out_v, float *w_scratch, int32_t B, void *stream);
 
 /*
+ * Added under ABI 10 (DCLL_ABI_VERSION is unchanged: a caller detects these three symbols by symbol lookup) — dcll_conv_lif_step_any
+ * for the layers of 33 .. 64 output channels that a --netscale above 1 makes (k_lif_step_wide, csrc/dcll_step_wide.hip): the same
+ * arguments, results, alignment rule (4 bytes, w_scratch included) and DCLL_ERR_INVALID cases.  Additions only: the default
+ * dispatch, dcll_conv_lif_step_any, their launch logs and refusals (that call's "c_out <= 32" included) are unchanged.
+ * Served (else DCLL_ERR_UNSUPPORTED, before any launch): stride = dilation = groups = 1; any c_in; c_out <= 64; kh, kw <= 16; any
+ * padding, pooling and batch; and a working set within the 160 KiB of LDS of a workgroup:
+ *   4 bytes x (c_in (h + 2 pad_h)(w + 2 pad_w) [zero-padded eps1 image] + (pooling != 1 ? c_out ch cw : 0) [v plane of the
+ *   pooling pass] + 64 [bias]).
+ * dcll_conv_lif_step_wide_lds returns these bytes, dcll_conv_lif_step_wide_scratch the floats of w_scratch — 128 per MFMA step of
+ * a chain, written by k_step_wide_wprep in front of the layer kernel on EVERY call —; both 0 for a descriptor that is not served.
+ * c_out <= 32: the call IS dcll_conv_lif_step_any — same kernels, launch log, bits, refusals (with that call's name in the
+ * message) and _lds / _scratch values — so a network of mixed widths goes through one entry point.
+ * c_out 33 .. 64: k_lif_step_any's decomposition and arithmetic with M = c_out padded to 64 rows, two 32-row tiles; each of the
+ * two chains of a pixel tile is the pinned order, unsplit; rows at or beyond c_out carry zero weights and are never stored.  v
+ * equals dcll_conv_lif_step bit for bit up to the sign of a zero; spikes, eps0, eps1 and arp bit for bit; pv within the sigmoid's
+ * 1e-4.
+ * Forms (the launch log names them; R = refractory; k_step_wide_wprep in front of each):
+ *   "k_lif_step_wide<R>"                      one workgroup per sample; a wave runs BOTH M tiles of its pixel tiles, one LDS read
+ *                                             of the B operand feeding two MFMAs
+ *   "k_lif_step_wide<R> (pooling)"            the same with the v plane and the pooling pass in LDS
+ *   "k_trace", "k_lif_step_wide<R> (split)"   NS > 1 workgroups per sample for a layer without pooling.  The unit is (pixel tile,
+ *                                             M tile), units = 2 ceil(ch cw / 32); ns0 = min(ceil(units / 4), 256 / B); ns0 <= 1:
+ *                                             fused; else upw = ceil(units / ns0), NS = ceil(units / upw), workgroup `part` runs
+ *                                             units [part upw, (part + 1) upw).  The traces advance in k_trace BEFORE the layer
+ *                                             kernel.  Results do not depend on NS.
+ */
+int64_t dcll_conv_lif_step_wide_lds(const dcll_conv_desc *d);
+int64_t dcll_conv_lif_step_wide_scratch(const dcll_conv_desc *d);
+int dcll_conv_lif_step_wide(const dcll_conv_desc *d, const float *x, const float *W, const float *b, const float *alpha,
+                            const float *tau_m, const float *alphas, const float *tau_s, float *eps0, float *eps1, float *arp,
+                            const float *i2o_W, const float *i2o_b, const float *out_W, const float *out_b, float *out_s,
+                            float *out_p, float *out_o, float *out_pv, float *out_v, float *w_scratch, int32_t B, void *stream);
+
+/*
  * Added under ABI 10 (DCLL_ABI_VERSION is unchanged: a caller detects these two symbols by symbol lookup) — one layer step of a
  * (1,3) / 64-channel / (1,2)-pool layer of radio_ml_conv_ref.yaml in one MFMA launch (k_lif_step_w3, csrc/dcll_step_w3.hip):
  * dcll_conv_lif_step_any's arguments without w_scratch, dcll_conv_lif_step's results.  Additions only: the default dispatch, its

@@ -180,6 +180,19 @@ int dcll_launch_step_any(const dcll_conv_desc *d, const float *x, const float *w
                          const float *tau_m, const float *alphas, const float *tau_s, float *eps0, float *eps1, float *arp,
                          float *out_s, float *out_pv, float *out_v, int ns, int32_t B, hipStream_t st, bool launch);
 
+// k_lif_step_wide (dcll_step_wide.hip): one MFMA layer step of a plain conv layer with 33 .. 64 output channels (kernel up to
+// 16x16), two 32-row M tiles.  _check: DCLL_OK or the refusal with its message (c_out <= 32: dcll_step_any_check's answer — the
+// entry point hands those layers to dcll_conv_lif_step_any, they never reach the launchers here); _split: workgroups per sample
+// (> 1: the caller runs k_trace first); _wprep: w_scratch in k_lif_step_wide's fragment order (128 floats per chain step); the
+// launcher with launch == false only prepares (checks, LDS reservation): called before the first launch of the entry point
+__attribute__((visibility("hidden"))) int dcll_step_wide_check(const dcll_conv_desc *d, const char *who);
+__attribute__((visibility("hidden"))) int dcll_step_wide_split(const dcll_conv_desc *d, int32_t B);
+__attribute__((visibility("hidden"))) int dcll_launch_step_wide_wprep(const dcll_conv_desc *d, const float *W, float *wperm, hipStream_t st);
+__attribute__((visibility("hidden")))
+int dcll_launch_step_wide(const dcll_conv_desc *d, const float *x, const float *wperm, const float *b, const float *alpha,
+                          const float *tau_m, const float *alphas, const float *tau_s, float *eps0, float *eps1, float *arp,
+                          float *out_s, float *out_pv, float *out_v, int ns, int32_t B, hipStream_t st, bool launch);
+
 // k_lif_step_w3 (dcll_step_w3.hip): one MFMA layer step of the layers dcll_seq_w3_geometry() serves.  _check: DCLL_OK or the
 // refusal with its message; _tiles: tiles per workgroup (8 or 4) for (descriptor, B); the launcher with launch == false only
 // prepares (checks, LDS reservation): called before the first launch of the entry point

@@ -289,6 +289,10 @@ class ContinuousConv2D(nn.Module):
     # _step: dcll_conv_lif_step_w3 (k_lif_step_w3) instead; opt-in through ConvNetwork.w3_step_path, which asks
     # w3_step_supported() first.  Set here directly the same holds: a layer the library refuses raises, there is no fall-back
     w3_step_path = False
+    # _step: dcll_conv_lif_step_wide (k_lif_step_wide: layers of up to 64 output channels; c_out <= 32 runs k_lif_step_any)
+    # instead; opt-in through ConvNetwork.wide_step_path, which asks step_wide_supported() first.  Set here directly the same
+    # holds: a layer the library refuses raises, there is no fall-back
+    wide_step_path = False
 
     def _step(self, input, pooling=(1, 1), i2o=None, output_=None, out=None, stacked=None, finish=None, want_v=True,
               defer_ro=False):
@@ -307,7 +311,7 @@ class ContinuousConv2D(nn.Module):
                 None if i2o is None else i2o.weight, None if i2o is None else i2o.bias,
                 None if output_ is None else output_.weight, None if output_ is None else output_.bias, out=out,
                 q8=self.int8_weights(), stacked=stacked, finish=finish, want_v=want_v, defer_ro=defer_ro,
-                any_path=self.any_step_path, w3_path=self.w3_step_path)
+                any_path=self.any_step_path, w3_path=self.w3_step_path, wide_path=self.wide_step_path)
 
     def _general(self):
         """True when the layer was built with an option outside the fused step (see _is_sigmoid)."""
@@ -697,6 +701,15 @@ class Conv2dDCLLlayer(nn.Module):
         if i._general() or i.int8_weights() is not None:
             return False
         return ops.step_any_supported(i.make_desc(self.im_dims, self.pooling, self.target_size, self.output_layer))
+
+    # -- the MFMA per-step forward of the layers of up to 64 output channels (k_lif_step_wide): opt-in through i2h.wide_step_path
+    def step_wide_supported(self):
+        """True if dcll_conv_lif_step_wide serves this layer's steps: as step_any_supported with up to 64 output channels
+        (ops.step_wide_supported; c_out <= 32 runs k_lif_step_any)."""
+        i = self.i2h
+        if i._general() or i.int8_weights() is not None:
+            return False
+        return ops.step_wide_supported(i.make_desc(self.im_dims, self.pooling, self.target_size, self.output_layer))
 
     # -- the MFMA per-step forward and weight gradient of the (1,3) / 64-channel layers (k_lif_step_w3, k_bwd_wgrad_w3) ------
     def w3_step_supported(self):
@@ -1204,6 +1217,11 @@ class DCLLBase(nn.Module):
         """True if this slice's layer steps can run on k_lif_step_any (Conv2dDCLLlayer.step_any_supported)."""
         L = self.dclllayer
         return isinstance(L, Conv2dDCLLlayer) and L.step_any_supported()
+
+    def step_wide_supported(self):
+        """True if this slice's layer steps can run on k_lif_step_wide (Conv2dDCLLlayer.step_wide_supported)."""
+        L = self.dclllayer
+        return isinstance(L, Conv2dDCLLlayer) and L.step_wide_supported()
 
     def _backward_from_pv(self):
         """True if this slice's backward can take sigmoid' from pv: no pooling, <= 32 readout rows (k_bwd_dv_nopool)."""

@@ -308,6 +308,7 @@ class ConvNetwork(torch.nn.Module):
             sig.append(bool(s.any_learning_path))
             sig.append(bool(s.wide_learning_path))
             sig.append(bool(L.i2h.any_step_path))
+            sig.append(bool(L.i2h.wide_step_path))
             sig.append((bool(s.w3_learning_path), bool(L.i2h.w3_step_path), bool(s.w3_first_wgrad), bool(s.w3_dv)))
             for t in s._adam_tensors(advance=False):
                 sig += [t['param'].data_ptr(), t['grad'].data_ptr(), t['exp_avg'].data_ptr(),
@@ -531,6 +532,7 @@ class ConvNetwork(torch.nn.Module):
             sig.append(None if q8 is None else (q8[0].data_ptr(), q8[1].data_ptr()))
             sig.append(bool(L.i2h.any_step_path))
             sig.append(bool(L.i2h.w3_step_path))
+            sig.append(bool(L.i2h.wide_step_path))
         return tuple(sig)
 
     @torch.no_grad()
@@ -586,14 +588,23 @@ class ConvNetwork(torch.nn.Module):
         """DCLL_ANY_STEP_PATH=1 in the environment = `net.any_step_path = True` at the network's first reset(True), for the entry
         points without a flag of their own (test_radio_ml.py: `DCLL_ANY_STEP_PATH=1 python test_radio_ml.py --no_sequence_path`
         runs its per-step loop on k_lif_step_any).  Ignored with a notice where a layer is not served; unset or 0: nothing
-        changes.  Looked at once per network, so a later `net.any_step_path = False` holds."""
-        if self.__dict__.get('_any_step_env_seen') or os.environ.get('DCLL_ANY_STEP_PATH', '0') in ('', '0'):
-            return
-        self.__dict__['_any_step_env_seen'] = True
-        if self.step_any_supported():
-            self.any_step_path = True
-        else:
-            print('DCLL_ANY_STEP_PATH ignored: k_lif_step_any does not serve every layer of this network')
+        changes.  Looked at once per network, so a later `net.any_step_path = False` holds.
+        DCLL_WIDE_STEP_PATH=1 = `net.wide_step_path = True` (k_lif_step_wide: layers of up to 64 output channels) by the same
+        rule; together with DCLL_ANY_STEP_PATH=1 the latter wins where it is served and this one is ignored with a notice."""
+        if not (self.__dict__.get('_any_step_env_seen') or os.environ.get('DCLL_ANY_STEP_PATH', '0') in ('', '0')):
+            self.__dict__['_any_step_env_seen'] = True
+            if self.step_any_supported():
+                self.any_step_path = True
+            else:
+                print('DCLL_ANY_STEP_PATH ignored: k_lif_step_any does not serve every layer of this network')
+        if not (self.__dict__.get('_wide_step_env_seen') or os.environ.get('DCLL_WIDE_STEP_PATH', '0') in ('', '0')):
+            self.__dict__['_wide_step_env_seen'] = True
+            if not self.step_wide_supported():
+                print('DCLL_WIDE_STEP_PATH ignored: k_lif_step_wide does not serve every layer of this network')
+            elif self.w3_step_path or any(s.dclllayer.i2h.any_step_path for s in self.dcll_slices):
+                print('DCLL_WIDE_STEP_PATH ignored: another per-step path (any_step_path / w3_step_path) is on')
+            else:
+                self.wide_step_path = True
 
     def write_stats(self, writer, epoch, comment=''):
         for s in self.dcll_slices:
@@ -932,10 +943,38 @@ class ConvNetwork(torch.nn.Module):
         on = bool(on)
         if on and self.w3_step_path:
             raise ops._lib.DCLLUnsupported('any_step_path cannot be combined with w3_step_path')
+        if on and any(s.dclllayer.i2h.wide_step_path for s in self.dcll_slices):
+            raise ops._lib.DCLLUnsupported('any_step_path cannot be combined with wide_step_path')
         if on and not self.step_any_supported():
             raise ops._lib.DCLLUnsupported('dcll_conv_lif_step_any does not serve every layer of this network')
         for s in self.dcll_slices:
             s.dclllayer.i2h.any_step_path = on  # (part of _graph_signature and _test_signature: a capture of the other path is retaken)
+
+    # -- the MFMA per-step forward of layers with up to 64 output channels (k_lif_step_wide): opt-in, beside the default dispatch --
+    def step_wide_supported(self):
+        """True if every layer's steps are served by dcll_conv_lif_step_wide (Conv2dDCLLlayer.step_wide_supported)."""
+        return all(s.step_wide_supported() for s in self.dcll_slices)
+
+    @property
+    def wide_step_path(self):
+        """True: every per-step layer call — net.test(x[t]), every learning timestep, Conv2dDCLLlayer.forward, the autograd
+        nodes — runs dcll_conv_lif_step_wide: k_lif_step_wide (k_lif_step_any's form with two 32-row M tiles) for the layers of
+        33 .. 64 output channels that a netscale above 1 makes, k_lif_step_any for the narrower ones, instead of
+        dcll_conv_lif_step's dispatch.  The readout tails and the sequence calls are untouched; combines with
+        wide_learning_path, any_learning_path and the default learning path.  Default False; setting it on a network that is
+        not fully served (c_out above 64, int8 weights), or together with any_step_path or w3_step_path, raises DCLLUnsupported
+        and leaves it off; switching it off is always allowed."""
+        return all(s.dclllayer.i2h.wide_step_path for s in self.dcll_slices)
+
+    @wide_step_path.setter
+    def wide_step_path(self, on):
+        on = bool(on)
+        if on and (self.w3_step_path or any(s.dclllayer.i2h.any_step_path for s in self.dcll_slices)):
+            raise ops._lib.DCLLUnsupported('wide_step_path cannot be combined with any_step_path / w3_step_path')
+        if on and not self.step_wide_supported():
+            raise ops._lib.DCLLUnsupported('dcll_conv_lif_step_wide does not serve every layer of this network')
+        for s in self.dcll_slices:
+            s.dclllayer.i2h.wide_step_path = on # (part of _graph_signature and _test_signature: a capture of the other path is retaken)
 
     # -- the MFMA learning step of the (1,3) / 64-channel layers of radio_ml_conv_ref.yaml: opt-in, beside the default dispatch --
     def w3_step_supported(self):
@@ -963,6 +1002,8 @@ class ConvNetwork(torch.nn.Module):
             raise ops._lib.DCLLUnsupported('w3_step_path cannot be combined with any_step_path / any_learning_path')
         if on and any(s.wide_learning_path for s in self.dcll_slices):
             raise ops._lib.DCLLUnsupported('w3_step_path cannot be combined with wide_learning_path')
+        if on and any(s.dclllayer.i2h.wide_step_path for s in self.dcll_slices):
+            raise ops._lib.DCLLUnsupported('w3_step_path cannot be combined with wide_step_path')
         if on and not self.w3_step_supported():
             raise ops._lib.DCLLUnsupported('dcll_conv_lif_step_w3 / dcll_conv_lif_backward_w3 do not serve every layer of this '
                                            'network')

@@ -112,7 +112,7 @@ def _check_layer_operands(desc, W, b, eps0, eps1, arp, B, tau=None, tau4=None):
 
 def conv_lif_step(desc, x, W, b, alpha, tau_m, alphas, tau_s, eps0, eps1, arp, i2o_W=None, i2o_b=None,
                   out_W=None, out_b=None, want_v=True, out=None, q8=None, stacked=None, finish=None, defer_ro=False,
-                  any_path=False, w3_path=False):
+                  any_path=False, w3_path=False, wide_path=False):
     """One Conv2dDCLLlayer.forward step (dcll/pytorch_libdcll.py:599-608); state tensors are updated in place.
 
     Returns (s_pooled, p, o, pv_pooled, v) — p / o are None when the corresponding weights are None.
@@ -133,7 +133,13 @@ def conv_lif_step(desc, x, W, b, alpha, tau_m, alphas, tau_s, eps0, eps1, arp, i
     `w3_path`: the layer kernel is dcll_conv_lif_step_w3 — k_lif_step_w3, one launch with the traces, the fp32-MFMA chains and the
     (1,2) pooling fused in, for the (1,3)-kernel / 64-channel layers of radio_ml_conv_ref.yaml (step_w3_supported); the readout
     tails are the same.  fp32 weights only; combined with `any_path` or `q8` it raises.
+    `wide_path`: the layer kernel is dcll_conv_lif_step_wide — k_lif_step_wide, k_lif_step_any's form with two 32-row M tiles, for
+    a plain conv layer with up to 64 output channels (step_wide_supported); a layer with c_out <= 32 runs the `any_path`
+    kernels, same bits and launch log.  fp32 weights only; combined with `q8`, `any_path` or `w3_path` it raises.
     """
+    if wide_path and (q8 is not None or any_path or w3_path):
+        raise ValueError("conv_lif_step(wide_path=True) cannot be combined with q8, any_path=True or w3_path=True (fp32 weights, "
+                         "one layer kernel)")
     if any_path and q8 is not None:
         raise ValueError("conv_lif_step(any_path=True) reads fp32 weights only (no q8)")
     if w3_path and (any_path or q8 is not None):
@@ -166,14 +172,17 @@ def conv_lif_step(desc, x, W, b, alpha, tau_m, alphas, tau_s, eps0, eps1, arp, i
     v = buf('v', (B, desc.c_out, ch, cw), want_v)
     p = buf('p', (B, desc.target), i2o_W is not None)
     o = buf('o', (B, desc.target), bool(desc.output_layer))
-    scratch = buf('scratch', (2, B, desc.c_out, ch, cw), pooled and not any_path and not w3_path)
+    scratch = buf('scratch', (2, B, desc.c_out, ch, cw), pooled and not any_path and not w3_path and not wide_path)
     w_scratch = buf('w_scratch', (max(step_any_scratch(desc), 1),), True) if any_path else None       # (not served: the call refuses)
+    if wide_path:
+        w_scratch = buf('w_scratch', (max(step_wide_scratch(desc), 1),), True)
 
     def layer_step(d, *readout_args):
-        """the layer call of this step: dcll_conv_lif_step, dcll_conv_lif_step_any (w_scratch for scratch, no opts) or
+        """the layer call of this step: dcll_conv_lif_step, dcll_conv_lif_step_any / _wide (w_scratch for scratch, no opts) or
         dcll_conv_lif_step_w3 (neither)"""
-        fn = "dcll_conv_lif_step_w3" if w3_path else "dcll_conv_lif_step_any" if any_path else "dcll_conv_lif_step"
-        tail = () if w3_path else (ptr(w_scratch),) if any_path else (ptr(scratch), opts)
+        fn = ("dcll_conv_lif_step_w3" if w3_path else "dcll_conv_lif_step_any" if any_path else
+              "dcll_conv_lif_step_wide" if wide_path else "dcll_conv_lif_step")
+        tail = () if w3_path else (ptr(w_scratch),) if any_path or wide_path else (ptr(scratch), opts)
         rc = getattr(_lib.get(), fn)(
             ctypes.byref(d), ptr(x), ptr(W), ptr(b), ptr(alpha), ptr(tau_m), ptr(alphas), ptr(tau_s),
             ptr(eps0), ptr(eps1), ptr(arp), *readout_args, ptr(pv), ptr(v), *tail, B, stream_ptr())
@@ -230,6 +239,24 @@ def step_any_supported(desc):
 def step_any_scratch(desc):
     """Floats of dcll_conv_lif_step_any's w_scratch (dcll_conv_lif_step_any_scratch: 64 per MFMA step of a chain), 0 = not served."""
     return int(_lib.get().dcll_conv_lif_step_any_scratch(ctypes.byref(desc)))
+
+
+def step_wide_lds(desc):
+    """LDS bytes per workgroup of k_lif_step_wide on this layer (c_out <= 32: step_any_lds), 0 = the layer is not served
+    (dcll_conv_lif_step_wide_lds)."""
+    return int(_lib.get().dcll_conv_lif_step_wide_lds(ctypes.byref(desc)))
+
+
+def step_wide_supported(desc):
+    """True if conv_lif_step(wide_path=True) serves the layer: a plain conv with c_out <= 64, a kernel up to 16x16 and a working
+    set (the zero-padded eps1 image, the v plane of a pooling layer) within the 160 KiB of LDS."""
+    return step_wide_lds(desc) > 0
+
+
+def step_wide_scratch(desc):
+    """Floats of dcll_conv_lif_step_wide's w_scratch (dcll_conv_lif_step_wide_scratch: 128 per MFMA step of a chain; c_out <= 32:
+    step_any_scratch), 0 = not served."""
+    return int(_lib.get().dcll_conv_lif_step_wide_scratch(ctypes.byref(desc)))
 
 
 def step_w3_lds(desc):

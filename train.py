@@ -110,6 +110,19 @@ def parse_args(argv=None):
                         'a kernel up to 16x16) where ConvNetwork.step_any_supported() holds; ignored with a notice elsewhere.  '
                         'The sequence paths are not affected.  Not yet measured against the default path (DESIGN 4.2b; '
                         'experiments/step_any_timing.py)')
+    p.add_argument('--wide_step_path', action='store_true',
+                   help='opt in: every per-step layer call (net.test per timestep, every learning timestep) runs through '
+                        'dcll_conv_lif_step_wide — k_lif_step_wide (k_lif_step_any\'s form with two 32-row M tiles) for layers of 33-64 '
+                        'output channels (--netscale up to 2), k_lif_step_any up to 32 — where ConvNetwork.step_wide_supported() '
+                        'holds; ignored with a notice elsewhere and together with --any_step_path / --w3_step_path; combines with '
+                        '--wide_learning_path.  The sequence paths are not affected.  Measured on an MI355X against the same tree '
+                        'without the flag, --wide_learning_path in both arms, five alternating fresh processes, min-max ms per '
+                        'timestep: radio_ml_conv.yaml at netscale 2 on 16x16: net.test 0.491-0.497 -> 0.426-0.459 at B = 64 '
+                        '(1.07-1.17x), 2.672-2.683 -> 1.374-1.378 at B = 512 (1.94-1.95x); net.learn 0.756-0.759 -> 0.693-0.695 at '
+                        'B = 64 (1.09-1.10x), 4.350-4.528 -> 2.961-2.987 at B = 512 (1.46-1.53x); mnist_conv.yaml at netscale 2: '
+                        'net.learn 2.395-2.413 -> 1.263-1.288 at B = 512 (1.86-1.91x), but NOT faster at B = 32: 0.440-0.441 -> '
+                        '0.445-0.447 (one workgroup per sample leaves CUs idle in the layers that are not split) (DESIGN 4.2e; '
+                        'profiles/r21_step_wide_timing.txt; experiments/step_wide_timing.py)')
     p.add_argument('--w3_step_path', action='store_true',
                    help='opt in (radio_ml_conv_ref.yaml: the 64-channel layers with kernel (1,3), padding (0,1), pooling (1,2)): '
                         'every per-step layer call runs k_lif_step_w3 (traces, fp32-MFMA chains and pooling in one launch) and '
@@ -198,6 +211,7 @@ def main(argv=None):
     _opt_in_any_learning(net, args)
     _opt_in_any_step(net, args)
     _opt_in_w3_step(net, args)
+    _opt_in_wide_step(net, args)
     _opt_in_wide_learning(net, args)
     parallel.freeze_startup_heap()          # (a full GC pass over the start-up heap costs ~100 ms inside the T-loop)
 
@@ -398,6 +412,19 @@ def _opt_in_any_step(net, args):
         print('--any_step_path ignored: k_lif_step_any does not serve every layer of this network')
 
 
+def _opt_in_wide_step(net, args):
+    """--wide_step_path: switch the network's per-step layer calls to dcll_conv_lif_step_wide (k_lif_step_wide for layers of 33-64
+    output channels, k_lif_step_any below) where every layer is served and no other per-step path is in effect."""
+    if not getattr(args, 'wide_step_path', False):
+        return
+    if net.any_step_path or net.w3_step_path:
+        print('--wide_step_path ignored: another per-step path (--any_step_path / --w3_step_path) is in effect')
+    elif net.step_wide_supported():
+        net.wide_step_path = True
+    else:
+        print('--wide_step_path ignored: k_lif_step_wide does not serve every layer of this network')
+
+
 def _opt_in_w3_step(net, args):
     """--w3_step_path: switch the network's per-step layer calls and weight gradients to k_lif_step_w3 / k_bwd_wgrad_w3 where
     every layer is served; --w3_first_wgrad with it: the first layer's weight gradient on k_bwd_wgrad_w3f; --w3_dv_path with it:
@@ -449,6 +476,7 @@ def main_mnist(args):
     _opt_in_any_learning(net, args)
     _opt_in_any_step(net, args)
     _opt_in_w3_step(net, args)
+    _opt_in_wide_step(net, args)
     _opt_in_wide_learning(net, args)
     use_wide = _opt_in_wide_sequence(net, args, net.sequence_supported())      # (the condition of --any_sequence_path below)
     parallel.freeze_startup_heap()          # (a full GC pass over the start-up heap costs ~100 ms inside the T-loop)
