@@ -560,6 +560,44 @@ int dcll_conv_lif_sequence_wide(const dcll_conv_desc *d, const uint32_t *spk_in,
                                 float *v_out, float *w_scratch, int32_t T, int32_t B, void *stream);
 
 /*
+ * Still ABI 10 (four more symbols, found by lookup) — dcll_conv_lif_sequence_wide with SEVERAL workgroups per sample
+ * (k_lif_seq_band): a sample is cut into `bands` bands of output rows, each band sits on its own workgroup for all T and
+ * recomputes the input traces of the halo rows it needs; nothing passes between workgroups during the sequence.  For small batches
+ * (one workgroup per sample leaves CUs idle) and for layers whose per-sample state is beyond one workgroup's 160 KiB of LDS
+ * (radio_ml_conv.yaml on 48x48).  Arguments, buffer formats, arithmetic and results are dcll_conv_lif_sequence_wide's: every v is
+ * ONE unsplit chain in the pinned order, so v, pv, spikes and the final state are bit-identical to it wherever it serves the layer.
+ * Additions only: the calls above, their refusals and their kernels are unchanged.
+ *   bands     0: the library's rule — the smallest count that fits, raised while B x bands <= 256 (one round of the card) and
+ *             not beyond the count at which more bands stop paying: one band when the one-workgroup kernel already runs one chain
+ *             per wave (MT ceil(tiles / 8) == 1), several bands down to one 32-pixel tile per band; n >= 1: exactly n.
+ *             bands == 1 (asked for or chosen): the call is handed to dcll_conv_lif_sequence_wide unchanged (its kernels,
+ *             launch-log names, bits; its permuted weights are the scratch's prefix).
+ *   plan      band k of NB owns pooled rows [k ph / NB, (k + 1) ph / NB) (floor); its conv rows [C0, C1) are the union of those
+ *             pooling windows clipped to [0, ch), the last band's run up to ch; it holds input rows [C0 - pad_h, C1 - pad_h + kh - 1)
+ *             clipped to the image and writes the final eps0 / eps1 of rows [its first held row, the next band's first held row).
+ *   LDS       of a band, 4 bytes x (c_in (C1 - C0 + kh - 1)(w + 2 pad_w) + c_in (held rows) w + c_out (C1 - C0) cw + the same
+ *             again [arp, refractory layers only] + 4 c_in + 32 MT), MT = ceil(c_out / 32); the largest band's <= 160 KiB.
+ *   scratch   dcll_conv_lif_sequence_bands_scratch(d, B) floats = 64 MT per MFMA step of a chain (the permuted weights) +
+ *             2 B c_in h w: a stream-ordered copy of eps0 / eps1 in front of the launch, which every band's initial read goes to
+ *             (a late band of a grid beyond residency must not read a neighbour's final state as its halo).
+ *   spk_out   a band stores the words wholly inside its pooled-pixel range and ORs its bits into a word it shares with a
+ *             neighbour (atomicOr); when the plan has such a word, spk_out is zero-filled on the stream first.
+ * _plan: the band count the call would run (0 = refused); bounds, when not NULL, receives its bands + 1 pooled-row bounds.
+ * _lds: LDS bytes of the largest band (bands == 0: at the rule's count for B = 1; 1: dcll_conv_lif_sequence_wide_lds), 0 =
+ * refused.  _plan and _lds are host-only.  DCLL_ERR_UNSUPPORTED, before any launch: c_out > 64, stride / dilation / groups other
+ * than 1, a kernel beyond 16x16, bands > ph, an explicit band count whose largest set does not fit, no band count that fits.
+ * DCLL_ERR_INVALID, before any launch: bands < 0, a NULL required pointer, a refractory layer without arp, T < 0 or B < 0.
+ * T == 0 or B == 0: DCLL_OK, nothing is looked at.  Launch log: k_lif_seq_band<MT,R,WLDS> (M tiles, refractory, all weights in
+ * LDS); the weight permutation, the snapshot and the zero fill stay out of it.
+ */
+int32_t dcll_conv_lif_sequence_bands_plan(const dcll_conv_desc *d, int32_t B, int32_t bands, int32_t *bounds);
+int64_t dcll_conv_lif_sequence_bands_lds(const dcll_conv_desc *d, int32_t bands);
+int64_t dcll_conv_lif_sequence_bands_scratch(const dcll_conv_desc *d, int32_t B);
+int dcll_conv_lif_sequence_bands(const dcll_conv_desc *d, const uint32_t *spk_in, const float *W, const float *b,
+                                 const float *tau4, float *eps0, float *eps1, float *arp, uint32_t *spk_out, float *pv_out,
+                                 float *v_out, float *scratch, int32_t T, int32_t B, int32_t bands, void *stream);
+
+/*
  * ABI 9 — the backward of one layer step with the weight gradient of ANY plain conv layer on fp32-MFMA tiles (k_bwd_wgrad_any):
  * dcll_conv_lif_backward / dcll_conv_lif_backward_open with the same arguments, results and scratch rule (B c_out ch cw +
  * k (c_out (c_in kh kw + 1)) floats, k >= 1; less: DCLL_ERR_INVALID), for the layers whose weight gradient the calls above

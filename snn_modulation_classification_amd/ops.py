@@ -981,6 +981,47 @@ def conv_lif_sequence_wide(desc, spk_in, W, b, tau4, eps0, eps1, arp, T, B, want
                                    want_pv, want_v, out)
 
 
+def sequence_bands_plan(desc, B, bands=0):
+    """The band plan dcll_conv_lif_sequence_bands runs on this layer at batch B: the pooled-row bounds of its bands (a list of
+    bands + 1 ints), None = refused.  bands = 0: the library's rule; n >= 1: exactly n bands (host-only: no device is touched)."""
+    lib = _lib.get()
+    n = int(lib.dcll_conv_lif_sequence_bands_plan(ctypes.byref(desc), int(B), int(bands), None))
+    if n <= 0:
+        return None
+    bounds = (ctypes.c_int32 * (n + 1))()
+    lib.dcll_conv_lif_sequence_bands_plan(ctypes.byref(desc), int(B), int(bands), bounds)
+    return list(bounds)
+
+
+def sequence_bands_lds(desc, bands=0):
+    """LDS bytes of the largest band at this band count (0 = the rule's count for B = 1; 1: dcll_conv_lif_sequence_wide_lds),
+    0 = refused (dcll_conv_lif_sequence_bands_lds; host-only)."""
+    return int(_lib.get().dcll_conv_lif_sequence_bands_lds(ctypes.byref(desc), int(bands)))
+
+
+def sequence_bands_supported(desc, bands=0):
+    """True if dcll_conv_lif_sequence_bands serves the layer with this band count (0: with some band count): a plain conv with
+    c_out <= 64, a kernel up to 16x16 and the largest band's working set within a workgroup's LDS (include/dcll_hip.h)."""
+    return sequence_bands_lds(desc, bands) > 0
+
+
+def conv_lif_sequence_bands(desc, spk_in, W, b, tau4, eps0, eps1, arp, T, B, want_spikes=True, want_pv=True, want_v=False,
+                            out=None, bands=0):
+    """conv_lif_sequence_any through dcll_conv_lif_sequence_bands: `bands` workgroups per sample, each on a band of output rows
+    for all T (k_lif_seq_band; 0 = the library's rule, 1 = dcll_conv_lif_sequence_wide itself).  Same arguments, buffers and
+    results; its one scratch buffer (permuted weights + the snapshot of eps0 / eps1) is kept in `out` under 'band_scratch'."""
+    lib = _lib.get()
+    bands = int(bands)
+    if out is not None:             # (_conv_lif_sequence_call keeps its scratch under 'w_scratch': the siblings' buffer stays theirs)
+        out, mine = dict(out, w_scratch=out.get("band_scratch")), out
+    call = lambda *a: lib.dcll_conv_lif_sequence_bands(*(a[:-1] + (bands, a[-1])))
+    res = _conv_lif_sequence_call(call, lambda d: lib.dcll_conv_lif_sequence_bands_scratch(d, B), "dcll_conv_lif_sequence_bands",
+                                  desc, spk_in, W, b, tau4, eps0, eps1, arp, T, B, want_spikes, want_pv, want_v, out)
+    if out is not None:
+        mine["band_scratch"] = out["w_scratch"]
+    return res
+
+
 LOSS_KINDS = {"SmoothL1Loss": _lib.LOSS_SMOOTH_L1, "MSELoss": _lib.LOSS_MSE}
 
 

@@ -88,6 +88,14 @@ def parse_args(argv=None):
                         '(one workgroup per sample leaves CUs idle below 256 samples); mnist_conv.yaml at netscale 2, T = 50: '
                         '15.78-15.98 -> 13.62-13.76 at B = 32 (1.15x), 79.00-79.60 -> 29.03-29.09 at B = 512 (2.72x) (DESIGN 4.1e; '
                         'experiments/seq_wide_timing.py)')
+    p.add_argument('--band_sequence_path', type=int, nargs='?', const=0, default=None, metavar='N',
+                   help='opt in: the test phase of a network without a geometry-specialised sequence kernel runs '
+                        'ConvNetwork.test_sequence_any(bands=N) — dcll_conv_lif_sequence_bands, N workgroups per sample, each on a '
+                        'band of output rows for all T (k_lif_seq_band; N omitted or 0: the library\'s rule per layer; 1: '
+                        'dcll_conv_lif_sequence_wide itself).  Serves layers of up to 64 output channels, and planes whose '
+                        'per-sample state is beyond one workgroup\'s LDS (radio_ml_conv.yaml on 48x48).  One process only; ignored '
+                        'with a notice where the network is not served.  Wins over --any_sequence_path and --wide_sequence_path '
+                        'where more than one is given (DESIGN 4.1f; experiments/seq_band_timing.py)')
     p.add_argument('--any_learning_path', action='store_true',
                    help='opt in: every layer\'s weight gradient of the learning step runs on k_bwd_wgrad_any (fp32 MFMA; any '
                         'plain conv layer with c_out <= 32 and a kernel up to 16x16, which lifts the default path\'s 64-tap '
@@ -250,7 +258,9 @@ def main(argv=None):
     use_any = args.any_sequence_path and not use_sequence and world == 1 and net.sequence_any_supported()
     # --wide_sequence_path: the same with wide=True (layers of up to 64 output channels: a --netscale up to 2)
     use_wide = _opt_in_wide_sequence(net, args, use_sequence, world)
-    use_any = use_any or use_wide
+    # --band_sequence_path [N]: the same through dcll_conv_lif_sequence_bands; wins over the two above
+    use_bands = _opt_in_band_sequence(net, args, use_sequence, world)
+    use_any = use_any or use_wide or use_bands is not None
 
     def evaluate_batch_any(samples, labels1h):
         """The per-step branch of evaluate_batch (host-encoded planes, reference test_radio_ml.py:142-146) with its T-loop replaced
@@ -261,7 +271,7 @@ def main(argv=None):
                                         max_Q=args.Q_bounds[1], max_duration=T)
         net.reset()
         net.eval()
-        net.test_sequence_any(torch.Tensor(spikes).to(pytorch_libdcll.device)[:T], wide=use_wide)
+        net.test_sequence_any(torch.Tensor(spikes).to(pytorch_libdcll.device)[:T], wide=use_wide, bands=use_bands)
         return net.accuracy(torch.as_tensor(np.asarray(targets), dtype=torch.float32))
 
     def run_tests(step):
@@ -379,6 +389,26 @@ def _opt_in_wide_sequence(net, args, use_sequence, world=1):
     return False
 
 
+def _opt_in_band_sequence(net, args, use_sequence, world=1):
+    """--band_sequence_path [N]: the band count (0: the library's rule) where the test phase runs
+    ConvNetwork.test_sequence_any(bands=N) — the conditions of --wide_sequence_path with dcll_conv_lif_sequence_bands' predicate;
+    None elsewhere, with a notice where the flag was given."""
+    bands = getattr(args, 'band_sequence_path', None)
+    if bands is None:
+        return None
+    if use_sequence:
+        why = 'the network runs its geometry-specialised sequence kernels'
+    elif world > 1:
+        why = 'several ranks keep the sharded per-step evaluation'
+    elif bands < 0 or not net.sequence_any_supported(bands=bands):
+        why = 'dcll_conv_lif_sequence_bands does not serve every layer of this network with %s' % (
+            '%d bands' % bands if bands else 'any band count')
+    else:
+        return bands
+    print('--band_sequence_path ignored: ' + why)
+    return None
+
+
 def _opt_in_any_learning(net, args):
     """--any_learning_path: switch the network's learning step to k_bwd_wgrad_any where every slice is served."""
     if not args.any_learning_path:
@@ -479,6 +509,7 @@ def main_mnist(args):
     _opt_in_wide_step(net, args)
     _opt_in_wide_learning(net, args)
     use_wide = _opt_in_wide_sequence(net, args, net.sequence_supported())      # (the condition of --any_sequence_path below)
+    use_bands = _opt_in_band_sequence(net, args, net.sequence_supported())
     parallel.freeze_startup_heap()          # (a full GC pass over the start-up heap costs ~100 ms inside the T-loop)
     n_test = int(np.ceil(float(args.n_test_samples) / args.batch_size_test))
     if args.synthetic:
@@ -530,7 +561,9 @@ def main_mnist(args):
                 tx, ty = spikes_of(ts, tl, st_test)
                 net.reset()
                 net.eval()
-                if use_wide:
+                if use_bands is not None:
+                    net.test_sequence_any(tx[:args.n_iters_test], bands=use_bands)
+                elif use_wide:
                     net.test_sequence_any(tx[:args.n_iters_test], wide=True)
                 elif args.any_sequence_path and not net.sequence_supported() and net.sequence_any_supported():
                     net.test_sequence_any(tx[:args.n_iters_test])
