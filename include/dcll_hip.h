@@ -598,6 +598,51 @@ int dcll_conv_lif_sequence_bands(const dcll_conv_desc *d, const uint32_t *spk_in
                                  float *v_out, float *scratch, int32_t T, int32_t B, int32_t bands, void *stream);
 
 /*
+ * Still ABI 10 (four more symbols, found by lookup) — dcll_conv_lif_sequence_bands cut in BOTH directions (k_lif_seq_tile): a
+ * sample is cut into tiles_y x tiles_x tiles, each tile sits on its own workgroup for all T and recomputes the input traces of the
+ * halo rows and columns it needs; nothing passes between workgroups during the sequence.  For the layers no band count serves:
+ * a band spans full rows, so its LDS set grows with c_in kh (w + 2 pad_w) (radio_ml_conv.yaml at netscale 2 on any plane much wider
+ * than 16 pixels, at netscale 1 on 100x100).  Arguments, buffer formats, arithmetic and results are dcll_conv_lif_sequence_bands':
+ * every v is ONE unsplit chain in the pinned order, so v, pv, spikes and the final state are bit-identical to it wherever it serves
+ * the layer.  Additions only: the calls above, their refusals and their kernels are unchanged.
+ *   tiles     tiles_x == 1 (with any tiles_y, 0 included): the call is handed to dcll_conv_lif_sequence_bands unchanged with
+ *             bands = tiles_y (its kernels, launch-log names, bits, refusals; its scratch is this one's).
+ *             (0, 0): the library's rule — the plan of dcll_conv_lif_sequence_bands_plan(d, B, 0) where that serves the layer;
+ *             otherwise the fitting (NY, NX), NX >= 2, with the fewest tiles, ties to the smallest sum of held input elements over
+ *             all tiles, then to the smaller NX.  This rule is derived from the LDS formula alone: no measurement stands behind it.
+ *             tiles_y >= 1, tiles_x >= 2: exactly that plan.  A 0 in one place only: DCLL_ERR_INVALID.
+ *   plan      tile (a, b) of NY x NX takes its rows from the band plan above at (a, NY) and its columns from the same plan applied
+ *             to (b, NX, w, kw, pad_w, pool_w, cw, pw): owned pooled pixels, conv pixels (a partition; the floor-mode leftovers go
+ *             to the last tile of each direction), held input pixels, owned input pixels.  Every element of arp, v_out, pv_out,
+ *             every spike bit and every final eps0 / eps1 has exactly one owner.
+ *   LDS       of a tile of CR x CC conv pixels that holds HR x HC input pixels, 4 bytes x (c_in (CR + kh - 1)(CC + kw - 1) +
+ *             c_in HR HC + c_out CR CC + the same again [arp, refractory layers only] + 4 c_in + 32 MT), MT = ceil(c_out / 32); the
+ *             largest tile's <= 160 KiB.  Behind it as many permuted weight steps as fit, by dcll_conv_lif_sequence_bands' rule
+ *             (half of the LDS where B NY NX > 256 and the weights do not fit as a whole).  eps0 is kept in LDS.
+ *   scratch   dcll_conv_lif_sequence_tiles_scratch(d, B) floats = dcll_conv_lif_sequence_bands_scratch's formula: 64 MT per MFMA
+ *             step of a chain + 2 B c_in h w, the stream-ordered snapshot of eps0 / eps1 every tile's initial read goes to.
+ *   spk_out   a tile's pooled pixels are row segments of the flattened pooled plane.  A word wholly inside one segment is stored;
+ *             every other word is ORed into (atomicOr); when the plan has such a word, spk_out is zero-filled on the stream first.
+ *             Tail bits stay zero.
+ * _plan: the tile count NY NX the call would run (0 = refused); ny_nx, when not NULL, receives (NY, NX), bounds_y / bounds_x their
+ * NY + 1 pooled-row / NX + 1 pooled-column bounds.  _lds: LDS bytes of the largest tile ((0, 0): at the rule's plan for B = 1;
+ * tiles_x == 1: dcll_conv_lif_sequence_bands_lds(d, tiles_y)), 0 = refused.  _plan, _lds and _scratch are host-only.
+ * DCLL_ERR_UNSUPPORTED, before any launch: c_out > 64, stride / dilation / groups other than 1, a kernel beyond 16x16,
+ * tiles_y > ph or tiles_x > pw, an explicit plan whose largest set does not fit, no plan that fits.  DCLL_ERR_INVALID, before any
+ * launch: a negative count, a 0 in one place only, a NULL required pointer, a refractory layer without arp, T < 0 or B < 0,
+ * B NY NX beyond the grid.  T == 0 or B == 0: DCLL_OK, nothing is looked at.  Launch log: k_lif_seq_tile<MT,R,WLDS> (M tiles,
+ * refractory, all weights in LDS); the weight permutation, the snapshot and the zero fill stay out of it.
+ */
+int32_t dcll_conv_lif_sequence_tiles_plan(const dcll_conv_desc *d, int32_t B, int32_t tiles_y, int32_t tiles_x, int32_t *ny_nx,
+                                          int32_t *bounds_y, int32_t *bounds_x);
+int64_t dcll_conv_lif_sequence_tiles_lds(const dcll_conv_desc *d, int32_t tiles_y, int32_t tiles_x);
+int64_t dcll_conv_lif_sequence_tiles_scratch(const dcll_conv_desc *d, int32_t B);
+int dcll_conv_lif_sequence_tiles(const dcll_conv_desc *d, const uint32_t *spk_in, const float *W, const float *b,
+                                 const float *tau4, float *eps0, float *eps1, float *arp, uint32_t *spk_out, float *pv_out,
+                                 float *v_out, float *scratch, int32_t T, int32_t B, int32_t tiles_y, int32_t tiles_x,
+                                 void *stream);
+
+/*
  * ABI 9 — the backward of one layer step with the weight gradient of ANY plain conv layer on fp32-MFMA tiles (k_bwd_wgrad_any):
  * dcll_conv_lif_backward / dcll_conv_lif_backward_open with the same arguments, results and scratch rule (B c_out ch cw +
  * k (c_out (c_in kh kw + 1)) floats, k >= 1; less: DCLL_ERR_INVALID), for the layers whose weight gradient the calls above

@@ -151,6 +151,10 @@ SIGNATURES = {
     "dcll_conv_lif_sequence_bands_lds": (_I64, [_DP, _I32]),
     "dcll_conv_lif_sequence_bands_scratch": (_I64, [_DP, _I32]),
     "dcll_conv_lif_sequence_bands": (_I32, [_DP] + [_P] * 11 + [_I32, _I32, _I32, _P]),
+    "dcll_conv_lif_sequence_tiles_plan": (_I32, [_DP, _I32, _I32, _I32, _IP, _IP, _IP]),
+    "dcll_conv_lif_sequence_tiles_lds": (_I64, [_DP, _I32, _I32]),
+    "dcll_conv_lif_sequence_tiles_scratch": (_I64, [_DP, _I32]),
+    "dcll_conv_lif_sequence_tiles": (_I32, [_DP] + [_P] * 11 + [_I32, _I32, _I32, _I32, _P]),
     "dcll_pack_spike_planes": (_I32, [_P, _P, _I64, _I32, _P]),
     "dcll_unpack_spike_planes": (_I32, [_P, _P, _I64, _I32, _P]),
     "dcll_conv_lif_backward_any_lds": (_I64, [_DP]),

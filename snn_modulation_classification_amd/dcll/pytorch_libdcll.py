@@ -723,32 +723,38 @@ class Conv2dDCLLlayer(nn.Module):
         return ops.step_w3_supported(desc) and ops.backward_w3_supported(desc)
 
     # -- the fused path of any plain conv layer (k_lif_seq_any, ABI 8): opt-in, beside sequence_kind / forward_sequence ---
-    def sequence_any_supported(self, wide=False, bands=None):
+    def sequence_any_supported(self, wide=False, bands=None, tiles=None):
         """True if dcll_conv_lif_sequence_any serves this layer: built inside the fused step (not _general()), no active
         lc_dropout, time constants constant over (H, W), and the library's own predicate (plain conv, c_out <= 32, kernel up
         to 16x16, the per-sample working set within a workgroup's LDS).  wide=True: dcll_conv_lif_sequence_wide's predicate
         (c_out <= 64) instead.  bands = an int: dcll_conv_lif_sequence_bands' predicate at that band count (0: at some band
-        count) instead of either."""
+        count) instead of either.  tiles = (ty, tx): dcll_conv_lif_sequence_tiles' predicate at that tile plan ((0, 0): at some
+        plan) instead of all three."""
         i = self.i2h
         if i._general() or self.dropout_active() or i.tau_per_channel() is None:
             return False
         desc = i.make_desc(self.im_dims, self.pooling, self.target_size, self.output_layer)
+        if tiles is not None:
+            return ops.sequence_tiles_supported(desc, tiles)
         if bands is not None:
             return ops.sequence_bands_supported(desc, bands)
         return ops.sequence_wide_supported(desc) if wide else ops.sequence_any_supported(desc)
 
     def forward_sequence_any(self, x_packed, T, B, want_spikes=True, want_pv=True, want_v=False, buffers=None,
-                             batch_slice=None, wide=False, bands=None):
+                             batch_slice=None, wide=False, bands=None, tiles=None):
         """All T steps in one launch of k_lif_seq_any (wide=True: through dcll_conv_lif_sequence_wide — k_lif_seq_wide for
         33-64 output channels).  x_packed: (T,B,C_in,ceil(H*W/32)) int32 spike planes
         (ops.pack_spike_planes).  Neuron state as in forward_sequence (rows batch_slice.. of it for a chunk of a batch).
         -> (pooled packed spikes (T,B,C,ceil(ph*pw/32)), pv (T,B,C,ph,pw), v (T,B,C,ch,cw)), None where not wanted.
         bands = an int: through dcll_conv_lif_sequence_bands with that many workgroups per sample (k_lif_seq_band; 0: the
-        library's rule; 1: dcll_conv_lif_sequence_wide itself); None: the calls above."""
+        library's rule; 1: dcll_conv_lif_sequence_wide itself); None: the calls above.
+        tiles = (ty, tx): through dcll_conv_lif_sequence_tiles with ty x tx workgroups per sample (k_lif_seq_tile; (0, 0): the
+        library's rule; (ty, 1): dcll_conv_lif_sequence_bands itself); wins over bands and wide."""
         i2h = self.i2h
-        if not self.sequence_any_supported(wide=wide, bands=bands):
+        if not self.sequence_any_supported(wide=wide, bands=bands, tiles=tiles):
             raise ops._lib.DCLLUnsupported('dcll_conv_lif_sequence_%s does not serve this layer'
-                                           % ('bands' if bands is not None else 'wide' if wide else 'any'))
+                                           % ('tiles' if tiles is not None else 'bands' if bands is not None else 'wide' if wide
+                                              else 'any'))
         if batch_slice is None:
             if i2h.state is None or i2h.state.eps0.shape[0] != B:
                 i2h.init_state(B, self.im_dims)
@@ -760,6 +766,8 @@ class Conv2dDCLLlayer(nn.Module):
             call = ops.conv_lif_sequence_wide if wide else ops.conv_lif_sequence_any
             if bands is not None:
                 call = lambda *a, **kw: ops.conv_lif_sequence_bands(*a, bands=bands, **kw)
+            if tiles is not None:
+                call = lambda *a, **kw: ops.conv_lif_sequence_tiles(*a, tiles=tiles, **kw)
             return call(desc, x_packed, i2h.weight, i2h.bias, i2h.tau_per_channel(), st.eps0, st.eps1,
                         st.arp if len(st) > 2 else None, T, B, want_spikes=want_spikes, want_pv=want_pv, want_v=want_v,
                         out=buffers)

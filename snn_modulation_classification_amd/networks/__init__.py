@@ -1049,14 +1049,16 @@ class ConvNetwork(torch.nn.Module):
             s.w3_dv = on
 
     # -- the fused path of any plain conv network (k_lif_seq_any, ABI 8): opt-in, beside test_sequence ---------------------
-    def sequence_any_supported(self, wide=False, bands=None):
+    def sequence_any_supported(self, wide=False, bands=None, tiles=None):
         """True if every layer is served by dcll_conv_lif_sequence_any (Conv2dDCLLlayer.sequence_any_supported): any plain
         conv spec with at most 32 output channels per layer whose per-sample working set fits a workgroup's LDS —
         mnist_conv.yaml, radio_ml_conv.yaml on any small plane.  Independent of sequence_supported().  wide=True: served by
         dcll_conv_lif_sequence_wide, up to 64 output channels per layer (the same specs at --netscale up to 2).  bands = an
         int: served by dcll_conv_lif_sequence_bands at that band count (0: the library's rule) — up to 64 output channels, and
-        planes whose per-sample state is beyond one workgroup's LDS."""
-        return all(isinstance(s.dclllayer, Conv2dDCLLlayer) and s.dclllayer.sequence_any_supported(wide=wide, bands=bands)
+        planes whose per-sample state is beyond one workgroup's LDS.  tiles = (ty, tx): served by dcll_conv_lif_sequence_tiles at
+        that tile plan ((0, 0): the library's rule) — planes and layers too wide for any band count; wins over bands and wide."""
+        return all(isinstance(s.dclllayer, Conv2dDCLLlayer) and
+                   s.dclllayer.sequence_any_supported(wide=wide, bands=bands, tiles=tiles)
                    for s in self.dcll_slices)
 
     def _any_input_planes(self, x):
@@ -1081,7 +1083,7 @@ class ConvNetwork(torch.nn.Module):
         return ops.pack_spike_planes(x.to(torch.float32).reshape(T, B, C, H * W))
 
     @torch.no_grad()
-    def test_sequence_any(self, x, collect=True, keep_spikes=False, wide=False, bands=None):
+    def test_sequence_any(self, x, collect=True, keep_spikes=False, wide=False, bands=None, tiles=None):
         """Equivalent of `for t in range(T): net.test(x[t])` on the fused kernel of ANY plain conv layer (k_lif_seq_any):
         x = dense spike planes (T,B,C,H,W) on the device (any float or bool dtype; packed on the device), the same planes
         already packed ((T,B,C,ceil(H*W/32)) int32), or cell indices (T,B) for a one-channel first layer.  Every layer runs
@@ -1092,10 +1094,14 @@ class ConvNetwork(torch.nn.Module):
         wide=True: every layer call goes to dcll_conv_lif_sequence_wide (k_lif_seq_wide for 33-64 output channels,
         k_lif_seq_any up to 32); everything behind the layer calls is the same.
         bands = an int: every layer call goes to dcll_conv_lif_sequence_bands with that many workgroups per sample
-        (k_lif_seq_band; 0: the library's rule per layer; 1: dcll_conv_lif_sequence_wide itself); None: the calls above."""
-        if not self.sequence_any_supported(wide=wide, bands=bands):
+        (k_lif_seq_band; 0: the library's rule per layer; 1: dcll_conv_lif_sequence_wide itself); None: the calls above.
+        tiles = (ty, tx): every layer call goes to dcll_conv_lif_sequence_tiles with ty x tx workgroups per sample
+        (k_lif_seq_tile; (0, 0): the library's rule per layer; (ty, 1): dcll_conv_lif_sequence_bands itself); it wins over
+        bands and wide."""
+        if not self.sequence_any_supported(wide=wide, bands=bands, tiles=tiles):
             raise ops._lib.DCLLUnsupported('dcll_conv_lif_sequence_%s does not serve every layer of this network; '
-                                           'use net.test(x[t])' % ('bands' if bands is not None else 'wide' if wide else 'any'))
+                                           'use net.test(x[t])' % ('tiles' if tiles is not None else 'bands' if bands is not None
+                                                                   else 'wide' if wide else 'any'))
         T, B = int(x.shape[0]), int(x.shape[1])
         dev = x.device
         per_sample = 4 * T * max(s.dclllayer.out_channels * int(np.prod(s.dclllayer.output_shape)) for s in self.dcll_slices)
@@ -1109,7 +1115,7 @@ class ConvNetwork(torch.nn.Module):
                 if s.dclllayer.i2h.state is None or s.dclllayer.i2h.state.eps0.shape[0] != B:
                     s.dclllayer.i2h.init_state(B, s.dclllayer.im_dims)
             parts = [self._sequence_any_chunk(x[:, b0:min(B, b0 + chunk)], T, min(B, b0 + chunk) - b0, b0, keep_spikes, wide,
-                                              bands)
+                                              bands, tiles)
                      for b0 in range(0, B, chunk)]
             cat = lambda key, dim: [None if parts[0][key][i] is None else torch.cat([p[key][i] for p in parts], dim)
                                     for i in range(self.num_layers)]
@@ -1119,7 +1125,7 @@ class ConvNetwork(torch.nn.Module):
             if keep_spikes:
                 res['spikes'] = cat('spikes', 1)
         else:
-            res = self._sequence_any_chunk(x, T, B, None, keep_spikes, wide, bands)
+            res = self._sequence_any_chunk(x, T, B, None, keep_spikes, wide, bands, tiles)
         if collect:
             for i, s in enumerate(self.dcll_slices):
                 L = s.dclllayer
@@ -1127,7 +1133,7 @@ class ConvNetwork(torch.nn.Module):
                                       numel=B * L.out_channels * int(np.prod(L.output_shape)), vote=res['vote'][i])
         return res
 
-    def _sequence_any_chunk(self, x, T, B, batch_slice, keep_spikes, wide=False, bands=None):
+    def _sequence_any_chunk(self, x, T, B, batch_slice, keep_spikes, wide=False, bands=None, tiles=None):
         """All layers over all T steps for B samples (the whole batch, or rows batch_slice.. of every layer's state)."""
         for s in self.dcll_slices:
             i2h = s.dclllayer.i2h
@@ -1142,7 +1148,8 @@ class ConvNetwork(torch.nn.Module):
             L = s.dclllayer
             last = (i == self.num_layers - 1)
             spk, pv, _ = L.forward_sequence_any(cur, T, B, want_spikes=(not last) or keep_spikes, want_pv=True,
-                                                buffers=scratch.setdefault(i, {}), batch_slice=batch_slice, wide=wide, bands=bands)
+                                                buffers=scratch.setdefault(i, {}), batch_slice=batch_slice, wide=wide, bands=bands,
+                                                tiles=tiles)
             res['lowhigh'].append(ops.pv_lowhigh(pv.reshape(T, -1), T, s.iter) if s.collect_stats else None)
             if keep_spikes:
                 res['spikes'].append(spk)

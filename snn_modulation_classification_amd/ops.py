@@ -1022,6 +1022,58 @@ def conv_lif_sequence_bands(desc, spk_in, W, b, tau4, eps0, eps1, arp, T, B, wan
     return res
 
 
+def _tiles_pair(tiles):
+    """(tiles_y, tiles_x) of a `tiles` argument: a pair of ints"""
+    ty, tx = tiles
+    return int(ty), int(tx)
+
+
+def sequence_tiles_plan(desc, B, tiles=(0, 0)):
+    """The tile plan dcll_conv_lif_sequence_tiles runs on this layer at batch B: (pooled-row bounds, pooled-column bounds), two
+    lists of NY + 1 and NX + 1 ints, None = refused.  tiles = (0, 0): the library's rule (the band rule's plan where a band count
+    serves the layer, else the fitting plan of the fewest tiles — derived from the LDS formula alone, not measured); (ty, 1): ty
+    bands; (ty, tx): exactly that plan (host-only: no device is touched)."""
+    lib = _lib.get()
+    ty, tx = _tiles_pair(tiles)
+    nn = (ctypes.c_int32 * 2)()
+    if int(lib.dcll_conv_lif_sequence_tiles_plan(ctypes.byref(desc), int(B), ty, tx, nn, None, None)) <= 0:
+        return None
+    by, bx = (ctypes.c_int32 * (nn[0] + 1))(), (ctypes.c_int32 * (nn[1] + 1))()
+    lib.dcll_conv_lif_sequence_tiles_plan(ctypes.byref(desc), int(B), ty, tx, nn, by, bx)
+    return list(by), list(bx)
+
+
+def sequence_tiles_lds(desc, tiles=(0, 0)):
+    """LDS bytes of the largest tile of this plan ((0, 0): the rule's plan for B = 1; (ty, 1): dcll_conv_lif_sequence_bands_lds),
+    0 = refused (dcll_conv_lif_sequence_tiles_lds; host-only)."""
+    ty, tx = _tiles_pair(tiles)
+    return int(_lib.get().dcll_conv_lif_sequence_tiles_lds(ctypes.byref(desc), ty, tx))
+
+
+def sequence_tiles_supported(desc, tiles=(0, 0)):
+    """True if dcll_conv_lif_sequence_tiles serves the layer with this plan ((0, 0): with some plan): a plain conv with
+    c_out <= 64, a kernel up to 16x16 and the largest tile's working set within a workgroup's LDS (include/dcll_hip.h)."""
+    return sequence_tiles_lds(desc, tiles) > 0
+
+
+def conv_lif_sequence_tiles(desc, spk_in, W, b, tau4, eps0, eps1, arp, T, B, want_spikes=True, want_pv=True, want_v=False,
+                            out=None, tiles=(0, 0)):
+    """conv_lif_sequence_any through dcll_conv_lif_sequence_tiles: tiles = (ty, tx) workgroups per sample, each on a tile of the
+    output plane for all T (k_lif_seq_tile; (0, 0) = the library's rule, (ty, 1) = dcll_conv_lif_sequence_bands itself).  Same
+    arguments, buffers and results; its one scratch buffer (permuted weights + the snapshot of eps0 / eps1) is kept in `out` under
+    'tile_scratch'."""
+    lib = _lib.get()
+    ty, tx = _tiles_pair(tiles)
+    if out is not None:             # (_conv_lif_sequence_call keeps its scratch under 'w_scratch': the siblings' buffer stays theirs)
+        out, mine = dict(out, w_scratch=out.get("tile_scratch")), out
+    call = lambda *a: lib.dcll_conv_lif_sequence_tiles(*(a[:-1] + (ty, tx, a[-1])))
+    res = _conv_lif_sequence_call(call, lambda d: lib.dcll_conv_lif_sequence_tiles_scratch(d, B), "dcll_conv_lif_sequence_tiles",
+                                  desc, spk_in, W, b, tau4, eps0, eps1, arp, T, B, want_spikes, want_pv, want_v, out)
+    if out is not None:
+        mine["tile_scratch"] = out["w_scratch"]
+    return res
+
+
 LOSS_KINDS = {"SmoothL1Loss": _lib.LOSS_SMOOTH_L1, "MSELoss": _lib.LOSS_MSE}
 
 

@@ -96,6 +96,20 @@ def parse_args(argv=None):
                         'per-sample state is beyond one workgroup\'s LDS (radio_ml_conv.yaml on 48x48).  One process only; ignored '
                         'with a notice where the network is not served.  Wins over --any_sequence_path and --wide_sequence_path '
                         'where more than one is given (DESIGN 4.1f; experiments/seq_band_timing.py)')
+    p.add_argument('--tile_sequence_path', type=int, nargs='*', default=None, metavar='N',
+                   help='opt in, TY TX: the test phase of a network without a geometry-specialised sequence kernel runs '
+                        'ConvNetwork.test_sequence_any(tiles=(TY, TX)) — dcll_conv_lif_sequence_tiles, TY x TX workgroups per '
+                        'sample, each on a tile of the output plane for all T (k_lif_seq_tile; both omitted or 0 0: the library\'s '
+                        'rule per layer, derived from the LDS formula alone; TX = 1: dcll_conv_lif_sequence_bands itself with TY '
+                        'bands).  Serves the layers no band count serves: radio_ml_conv.yaml at netscale 2 on planes wider than '
+                        '16 pixels, at netscale 1 on planes that are no multiple of 8x32.  One process only; ignored with a notice '
+                        'where the network is not served.  Wins over --any_sequence_path, --wide_sequence_path and '
+                        '--band_sequence_path.  Measured on an MI355X, T = 128, per-step loop -> the rule, ms per sequence: netscale 2 '
+                        'on 24x40, B = 64: 251.56-254.38 -> 184.56-185.38 (faster, 1.36x), B = 512: 1878.74-1884.58 -> '
+                        '1435.98-1438.96 (faster, 1.31x); netscale 1 on 100x100, B = 64: 923.29-936.81 -> 460.72-462.17 (faster, '
+                        '2.00x); NOT faster at netscale 2 on 128x128, B = 64: 2608.86-2617.72 -> 3135.56-3149.17, and at netscale 1 '
+                        'on 48x48, B = 64: 68.86-69.88 -> 114.26-115.33 (the band rule; every tile plan is slower still) '
+                        '(DESIGN 4.1g; experiments/seq_tile_timing.py)')
     p.add_argument('--any_learning_path', action='store_true',
                    help='opt in: every layer\'s weight gradient of the learning step runs on k_bwd_wgrad_any (fp32 MFMA; any '
                         'plain conv layer with c_out <= 32 and a kernel up to 16x16, which lifts the default path\'s 64-tap '
@@ -260,7 +274,9 @@ def main(argv=None):
     use_wide = _opt_in_wide_sequence(net, args, use_sequence, world)
     # --band_sequence_path [N]: the same through dcll_conv_lif_sequence_bands; wins over the two above
     use_bands = _opt_in_band_sequence(net, args, use_sequence, world)
-    use_any = use_any or use_wide or use_bands is not None
+    # --tile_sequence_path [TY TX]: the same through dcll_conv_lif_sequence_tiles; wins over the three above
+    use_tiles = _opt_in_tile_sequence(net, args, use_sequence, world)
+    use_any = use_any or use_wide or use_bands is not None or use_tiles is not None
 
     def evaluate_batch_any(samples, labels1h):
         """The per-step branch of evaluate_batch (host-encoded planes, reference test_radio_ml.py:142-146) with its T-loop replaced
@@ -271,7 +287,8 @@ def main(argv=None):
                                         max_Q=args.Q_bounds[1], max_duration=T)
         net.reset()
         net.eval()
-        net.test_sequence_any(torch.Tensor(spikes).to(pytorch_libdcll.device)[:T], wide=use_wide, bands=use_bands)
+        net.test_sequence_any(torch.Tensor(spikes).to(pytorch_libdcll.device)[:T], wide=use_wide, bands=use_bands,
+                              tiles=use_tiles)
         return net.accuracy(torch.as_tensor(np.asarray(targets), dtype=torch.float32))
 
     def run_tests(step):
@@ -409,6 +426,36 @@ def _opt_in_band_sequence(net, args, use_sequence, world=1):
     return None
 
 
+def _tile_sequence_arg(args):
+    """--tile_sequence_path [TY TX] -> (ty, tx), None where the flag is absent (both omitted: (0, 0))"""
+    t = getattr(args, 'tile_sequence_path', None)
+    if t is None:
+        return None
+    if len(t) not in (0, 2):
+        raise SystemExit('--tile_sequence_path takes no value or two (TY TX)')
+    return (int(t[0]), int(t[1])) if t else (0, 0)
+
+
+def _opt_in_tile_sequence(net, args, use_sequence, world=1):
+    """--tile_sequence_path [TY TX]: the tile plan ((0, 0): the library's rule) where the test phase runs
+    ConvNetwork.test_sequence_any(tiles=(TY, TX)) — the conditions of --band_sequence_path with dcll_conv_lif_sequence_tiles'
+    predicate; None elsewhere, with a notice where the flag was given."""
+    tiles = _tile_sequence_arg(args)
+    if tiles is None:
+        return None
+    if use_sequence:
+        why = 'the network runs its geometry-specialised sequence kernels'
+    elif world > 1:
+        why = 'several ranks keep the sharded per-step evaluation'
+    elif min(tiles) < 0 or not net.sequence_any_supported(tiles=tiles):
+        why = 'dcll_conv_lif_sequence_tiles does not serve every layer of this network with %s' % (
+            '%d x %d tiles' % tiles if tiles != (0, 0) else 'any tile plan')
+    else:
+        return tiles
+    print('--tile_sequence_path ignored: ' + why)
+    return None
+
+
 def _opt_in_any_learning(net, args):
     """--any_learning_path: switch the network's learning step to k_bwd_wgrad_any where every slice is served."""
     if not args.any_learning_path:
@@ -510,6 +557,7 @@ def main_mnist(args):
     _opt_in_wide_learning(net, args)
     use_wide = _opt_in_wide_sequence(net, args, net.sequence_supported())      # (the condition of --any_sequence_path below)
     use_bands = _opt_in_band_sequence(net, args, net.sequence_supported())
+    use_tiles = _opt_in_tile_sequence(net, args, net.sequence_supported())
     parallel.freeze_startup_heap()          # (a full GC pass over the start-up heap costs ~100 ms inside the T-loop)
     n_test = int(np.ceil(float(args.n_test_samples) / args.batch_size_test))
     if args.synthetic:
@@ -561,7 +609,9 @@ def main_mnist(args):
                 tx, ty = spikes_of(ts, tl, st_test)
                 net.reset()
                 net.eval()
-                if use_bands is not None:
+                if use_tiles is not None:
+                    net.test_sequence_any(tx[:args.n_iters_test], tiles=use_tiles)
+                elif use_bands is not None:
                     net.test_sequence_any(tx[:args.n_iters_test], bands=use_bands)
                 elif use_wide:
                     net.test_sequence_any(tx[:args.n_iters_test], wide=True)
