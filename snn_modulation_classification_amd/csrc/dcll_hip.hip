@@ -3336,7 +3336,7 @@ extern "C" int dcll_conv_lif_step_any(const dcll_conv_desc *d, const float *x, c
     // (the launcher's own checks and its LDS reservation, nothing launched: an error return never leaves half-advanced state)
     rc = dcll_launch_step_any(d, x, w_scratch, b, alpha, tau_m, alphas, tau_s, eps0, eps1, arp, out_s, out_pv, out_v, ns, B, st, false);
     if (rc) return rc;
-    if ((rc = dcll_launch_seq_any_wprep(d, W, w_scratch, st)) != DCLL_OK) return rc;
+    if ((rc = dcll_launch_seq_wprep(d, W, w_scratch, 1, st, true)) != DCLL_OK) return rc;
     if (ns > 1) {       // split form: workgroups of one sample read each other's halo rows, so the traces advance BEFORE the kernel
         const long per = (long)d->c_in * d->h * d->w, nin = per * B;
         hipLaunchKernelGGL(k_trace, dim3(nblk(nin, 256) > 4096 ? 4096 : nblk(nin, 256)), dim3(256), 0, st, x, alpha, tau_m,

@@ -165,10 +165,13 @@ __attribute__((visibility("hidden")))
 int dcll_launch_bwd_wgrad_wide(const dcll_conv_desc *d, const float *gvf, const float *eps1, float *part, int32_t B,
                                long *nchunk, hipStream_t st);
 
-// k_seq_any_wprep (dcll_seq_any.hip): the weights of a plain conv layer in MFMA fragment order, 64 floats per chain step
-// (_steps: (c_in / 2) kh kw + (c_in odd: (kh kw + 1) / 2)) — shared by k_lif_seq_any and k_lif_step_any
-__attribute__((visibility("hidden"))) long dcll_seq_any_steps(const dcll_conv_desc *d);
-__attribute__((visibility("hidden"))) int dcll_launch_seq_any_wprep(const dcll_conv_desc *d, const float *W, float *wperm, hipStream_t st);
+// k_seq_any_wprep (dcll_seq_any.hip): the weights of a plain conv layer in MFMA fragment order, wperm[m][mt][lane], 64 MT floats
+// per chain step (any_chain_steps(), dcll_any_shared.h) — the one permutation of k_lif_seq_any / k_lif_step_any (MT = 1) and of
+// k_lif_seq_wide / k_lif_seq_band / k_lif_seq_tile.  note: the launch goes into the launch log (the MT = 1 entry points; the others
+// only collect the error); a failure's message starts with errname
+__attribute__((visibility("hidden")))
+int dcll_launch_seq_wprep(const dcll_conv_desc *d, const float *W, float *wperm, int MT, hipStream_t st, bool note,
+                          const char *errname = "k_seq_any_wprep");
 
 // k_lif_step_any (dcll_step_any.hip): one MFMA layer step of any plain conv layer (c_out <= 32, kernel up to 16x16).
 // _check: DCLL_OK or the refusal with its message; _split: workgroups per sample (> 1: the caller runs k_trace first);
@@ -327,7 +330,7 @@ struct any_div {
     uint32_t M;
     int d;
 };
-static inline any_div make_div(int d) { return any_div{d > 1 ? (uint32_t)(((1ull << 32) + d - 1) / d) : 0u, d}; }
+__host__ __device__ static inline any_div make_div(int d) { return any_div{d > 1 ? (uint32_t)(((1ull << 32) + d - 1) / d) : 0u, d}; }
 __device__ __forceinline__ int fdiv(int n, const any_div &q) { return q.d == 1 ? n : (int)__umulhi((uint32_t)n, q.M); }
 
 // A 32-bit LDS address the compiler cannot fold into static offsets (after `asm volatile("" : "+v"(p))`): reads through it are

@@ -32,11 +32,10 @@
 //   B  the chains: wave w computes pixel tiles w, w + 8, ... -> vpl
 //   C  refractory update on vpl (arp in LDS), v_out
 // State (eps0, eps1, arp) is read once before the first step and written once behind the last.
-#include "dcll_internal.h"
+#include "dcll_any_shared.h"
 
 constexpr int ANY_THREADS = 512, ANY_NW = ANY_THREADS / 64;
-constexpr long ANY_LDS_MAX = 160 * 1024;
-constexpr int ANY_MAX_K = 16, ANY_MAX_COUT = 32;
+constexpr int ANY_MAX_COUT = 32;
 constexpr int ANY_KE = 36, ANY_QMAX = 3;        // register form: eps0 values per thread, pixel tiles per wave
 
 struct any_geom {
@@ -60,11 +59,6 @@ static inline long any_lds_floats(const dcll_conv_desc *d)
     const long vpl = (long)d->c_out * ch * cw;
     return img + e0 + vpl * (d->refractory ? 2 : 1) + 4L * d->c_in + 32;
 }
-static inline long any_steps(const dcll_conv_desc *d)
-{
-    const long KK = (long)d->kh * d->kw;
-    return (d->c_in / 2) * KK + ((d->c_in & 1) ? (KK + 1) / 2 : 0);
-}
 
 // the register form's set: img + tau + bias; for layers without pooling within its per-thread / per-wave register arrays
 static inline long any_lds_floats_regs(const dcll_conv_desc *d)
@@ -82,11 +76,8 @@ static inline bool any_regs_ok(const dcll_conv_desc *d)
 // the support predicate: DCLL_OK (*regs: the register form serves the layer), or the refusal with its message
 static int any_supported(const dcll_conv_desc *d, const char *who, bool *regs = nullptr)
 {
-    int rc = check_desc(d);
+    int rc = any_layer_ok(d, ANY_MAX_COUT, who);
     if (rc) return rc;
-    if (!plain_conv(d)) return fail(DCLL_ERR_UNSUPPORTED, "plain convolutions only: stride, dilation and groups must be 1", who);
-    if (d->c_out > ANY_MAX_COUT) return fail(DCLL_ERR_UNSUPPORTED, "c_out <= 32 (one 32-row MFMA tile of output channels)", who);
-    if (d->kh > ANY_MAX_K || d->kw > ANY_MAX_K) return fail(DCLL_ERR_UNSUPPORTED, "kernels up to 16x16", who);
     const bool full = any_lds_floats(d) * 4 <= ANY_LDS_MAX;
     if (!full && !any_regs_ok(d))
         return fail(DCLL_ERR_UNSUPPORTED, "the per-sample working set (padded eps1 image, eps0, the v plane) exceeds the 160 KiB of LDS "
@@ -103,35 +94,31 @@ extern "C" int64_t dcll_conv_lif_sequence_any_lds(const dcll_conv_desc *d)
 }
 extern "C" int64_t dcll_conv_lif_sequence_any_scratch(const dcll_conv_desc *d)
 {
-    return any_supported(d, "dcll_conv_lif_sequence_any_scratch") == DCLL_OK ? any_steps(d) * 64 : 0;
+    return any_supported(d, "dcll_conv_lif_sequence_any_scratch") == DCLL_OK ? any_chain_steps(d) * 64 : 0;
 }
 
-// W (c_out, c_in, kh, kw) -> wperm[m][lane]: link 2 m + h of channel co = lane & 31, h = lane >> 5; 0 beyond c_out / the chain
+// W (c_out, c_in, kh, kw) -> wperm[m][mt][lane]: link 2 m + h of channel co = 32 mt + (lane & 31), h = lane >> 5; 0 beyond
+// c_out / the chain.  MT = 1: wperm[m][lane]
 __global__ void k_seq_any_wprep(const float *__restrict__ W, float *__restrict__ wperm, int c_in, int c_out, int kh, int kw,
-                                int npair, int nsteps)
+                                int npair, int nsteps, int MT)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nsteps * 64) return;
-    const int m = i >> 6, lane = i & 63, co = lane & 31, h = lane >> 5, KK = kh * kw;
+    if (i >= nsteps * 64 * MT) return;
+    const int lane = i & 63, u = i >> 6, mt = u % MT, m = u / MT, co = 32 * mt + (lane & 31), h = lane >> 5, KK = kh * kw;
     int ci, tap;
-    if (m < npair) {
-        ci = 2 * (m / KK) + h;
-        tap = m % KK;
-    } else {
-        ci = c_in - 1;
-        tap = 2 * (m - npair) + h;
-    }
+    any_link(m, h, npair, c_in, KK, ci, tap);
     wperm[i] = (co < c_out && tap < KK) ? W[((long)co * c_in + ci) * KK + tap] : 0.0f;
 }
 
-long dcll_seq_any_steps(const dcll_conv_desc *d) { return any_steps(d); }
-int dcll_launch_seq_any_wprep(const dcll_conv_desc *d, const float *W, float *wperm, hipStream_t st)
+int dcll_launch_seq_wprep(const dcll_conv_desc *d, const float *W, float *wperm, int MT, hipStream_t st, bool note,
+                          const char *errname)
 {
-    const int npair = (d->c_in / 2) * d->kh * d->kw, nsteps = (int)any_steps(d);
-    hipLaunchKernelGGL(k_seq_any_wprep, dim3((nsteps * 64 + 255) / 256), dim3(256), 0, st, W, wperm, d->c_in, d->c_out, d->kh, d->kw,
-                       npair, nsteps);
-    HIP_CHECK_LAUNCH("k_seq_any_wprep");
-    return DCLL_OK;
+    const int npair = (int)any_chain_pairs(d), nsteps = (int)any_chain_steps(d);
+    hipLaunchKernelGGL(k_seq_any_wprep, dim3((nsteps * 64 * MT + 255) / 256), dim3(256), 0, st, W, wperm, d->c_in, d->c_out, d->kh,
+                       d->kw, npair, nsteps, MT);
+    if (note) dcll_trace_note("k_seq_any_wprep");
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? DCLL_OK : fail(DCLL_ERR_LAUNCH, hipGetErrorString(e), errname);
 }
 
 template <bool R, bool WLDS, bool REGS>
@@ -434,8 +421,8 @@ extern "C" int dcll_conv_lif_sequence_any(const dcll_conv_desc *d, const uint32_
     conv_shape(d, &g.ch, &g.cw, &g.ph, &g.pw);
     g.CP = g.ch * g.cw;
     g.PP = g.ph * g.pw;
-    g.npair = (d->c_in / 2) * d->kh * d->kw;
-    g.nsteps = (int)any_steps(d);
+    g.npair = (int)any_chain_pairs(d);
+    g.nsteps = (int)any_chain_steps(d);
     g.iw = (d->h * d->w + 31) / 32;
     g.ow = (g.PP + 31) / 32;
     g.o_e0 = d->c_in * g.CHS;
@@ -448,16 +435,11 @@ extern "C" int dcll_conv_lif_sequence_any(const dcll_conv_desc *d, const uint32_
     const long base = g.o_w;
     if (base != (regs ? any_lds_floats_regs(d) : any_lds_floats(d)))        // the layout above against the ONE exported formula
         return fail(DCLL_ERR_LAUNCH, "LDS layout and dcll_conv_lif_sequence_any_lds disagree", who);
-    // weights that do not fit as a whole: a grid of more than one workgroup per CU (256 CUs) keeps half of the LDS free so that
-    // two samples share a CU — measured on mnist_conv.yaml's third layer at B = 512
-    const bool whole = (base + (long)g.nsteps * 64) * 4 <= ANY_LDS_MAX;
-    const long budget = (!whole && B > 256 && base * 4 * 2 <= ANY_LDS_MAX) ? ANY_LDS_MAX / 2 : ANY_LDS_MAX;
-    const long room = (budget / 4 - base) / 64;
-    g.nwl = (int)(room < g.nsteps ? room : g.nsteps);
+    g.nwl = seq_weight_room(base, g.nsteps, 1, B);
     const bool wlds = !regs && g.nwl == g.nsteps;
     const size_t lds_bytes = (size_t)(base + (long)g.nwl * 64) * 4;
 
-    if ((rc = dcll_launch_seq_any_wprep(d, W, w_scratch, st)) != DCLL_OK) return rc;
+    if ((rc = dcll_launch_seq_wprep(d, W, w_scratch, 1, st, true)) != DCLL_OK) return rc;
     // launch-log names: k_lif_seq_any<refractory, weights in LDS, register form>
 #define DCLL_ANY(R_, L_, G_)                                                                                                  \
     return launch_any<R_, L_, G_>(g, lds_bytes, spk_in, w_scratch, b, tau4, eps0, eps1, arp, spk_out, pv_out, v_out, T, B,    \

@@ -8,14 +8,9 @@
 // is still ONE unsplit chain in the pinned order: the results are bit-identical to the one-workgroup kernels.
 // bands = 1 hands the call to dcll_conv_lif_sequence_wide unchanged.
 //
-// Band plan (band_plan() is the ONE statement of it; tests/seq_band_cases.py restates it):
-//   band k of NB owns pooled rows [P0, P1) = [k ph / NB, (k + 1) ph / NB)                                     (floor)
-//   conv rows  [C0, C1): the union of those pooling windows (py pool_h - (pool_h - 1) / 2 + dy) clipped to [0, ch); the last
-//              band also takes the conv rows behind the last window (floor-mode pooling leaves such rows; their arp and v_out
-//              exist).  C0(k + 1) == C1(k): the conv rows are a partition.
-//   input rows held [I0, I1) = [C0 - pad_h, C1 - pad_h + kh - 1) clipped to [0, h]; rows outside the image are the zero padding
-//   input rows owned [O0, O1) = [I0(k), I0(k + 1)) (last band: up to h): the one band that writes an element's final eps0 / eps1
-//   arp, v_out of a conv pixel and pv, spike bit of a pooled pixel have one owner by construction.
+// Band plan: band_plan() of dcll_any_shared.h along the rows (tests/seq_band_cases.py restates it).  Band k of NB owns pooled rows
+// [P0, P1), computes conv rows [C0, C1), holds input rows [I0, I1) and writes the final eps0 / eps1 of input rows [O0, O1); arp,
+// v_out of a conv pixel and pv, spike bit of a pooled pixel have one owner by construction.
 //
 // LDS of a band (floats; band_floats() is the ONE statement of it, exported as dcll_conv_lif_sequence_bands_lds for the largest
 // band) — k_lif_seq_wide's LDS-form set on the band's rows:
@@ -35,41 +30,16 @@
 //     inside its pixel range and ORs its bits into a boundary word (an ordinary vector atomicOr); when the plan has such a word the
 //     launcher zero-fills spk_out on the stream first.  OR is commutative: the bits do not depend on the order.
 //
-// Arithmetic, weight permutation and phases are k_lif_seq_wide's (MT = 2) / k_lif_seq_any's (MT = 1), restated here: chain of
-// output (co, y, x) from bias[co] over the links (cp, ky, kx, h), one v_mfma_f32_32x32x2_f32 per two consecutive links; phases
-// A traces + pooling pass of t - 1 | B chains -> vpl | C refractory update + v_out, a barrier behind each.  The units of a band
-// are (32-pixel tile of the band's flattened conv rows, M tile): with at least 8 tiles a wave runs all MT chains of a tile on one
-// B read; with fewer, units go one per wave (an 8-wave workgroup with two tiles runs four chains at once).  Either way every
-// output's chain is whole and in order.
-#include "dcll_internal.h"
+// Arithmetic and phases are k_lif_seq_wide's (MT = 2) / k_lif_seq_any's (MT = 1).  Chain length, weight permutation, weights-in-LDS
+// budget, the launch prologue and the device code this kernel shares with k_lif_seq_tile (chain, to_vpl, phase C, constant
+// prologue) come from dcll_any_shared.h.  Phases: A traces + pooling pass of t - 1 | B chains -> vpl | C refractory update + v_out,
+// a barrier behind each.  The units of a band are (32-pixel tile of the band's flattened conv rows, M tile): with at least 8 tiles a
+// wave runs all MT chains of a tile on one B read; with fewer, units go one per wave (an 8-wave workgroup with two tiles runs four
+// chains at once).  Either way every output's chain is whole and in order.
+#include "dcll_any_shared.h"
 
 constexpr int BAND_THREADS = 512, BAND_NW = BAND_THREADS / 64;
-constexpr long BAND_LDS_MAX = 160 * 1024;
-constexpr int BAND_MAX_K = 16, BAND_MAX_COUT = 64;
-constexpr int BAND_CUS = 256;       // the default rule's device: an MI355X
-
-struct band_rows {
-    int P0, P1, C0, C1, I0, I1, O0, O1;
-};
-
-// the band plan: rows of band k of NB (1 <= NB <= ph)
-__host__ __device__ static inline band_rows band_plan(int k, int NB, int h, int kh, int pad_h, int pool_h, int ch, int ph)
-{
-    const int pph = (pool_h - 1) / 2;
-    band_rows r;
-    r.P0 = (int)((long)k * ph / NB);
-    r.P1 = (int)((long)(k + 1) * ph / NB);
-    const int c0 = r.P0 * pool_h - pph, c1 = r.P1 * pool_h - pph;   // first conv row of the windows of pooled rows P0, P1
-    r.C0 = c0 < 0 ? 0 : c0;
-    r.C1 = (k == NB - 1) ? ch : (c1 < 0 ? 0 : c1);                  // (P1 < ph: c1 < ch)
-    const int i0 = r.C0 - pad_h, i1 = r.C1 - pad_h + kh - 1;
-    r.I0 = i0 < 0 ? 0 : (i0 > h ? h : i0);
-    r.I1 = i1 < 0 ? 0 : (i1 > h ? h : i1);
-    const int o1 = r.C1 - pad_h;                                    // = I0 of band k + 1
-    r.O0 = r.I0;
-    r.O1 = (k == NB - 1) ? h : (o1 < 0 ? 0 : (o1 > h ? h : o1));
-    return r;
-}
+constexpr int BAND_MAX_COUT = 64;
 
 struct band_geom {
     int c_in, c_out, h, w, kh, kw, pad_h, pad_w, pool_h, pool_w;
@@ -126,27 +96,12 @@ static inline long band_floats_max(const dcll_conv_desc *d, int NB)
     }
     return m;
 }
-static inline long band_steps(const dcll_conv_desc *d)
-{
-    const long KK = (long)d->kh * d->kw;
-    return (d->c_in / 2) * KK + ((d->c_in & 1) ? (KK + 1) / 2 : 0);
-}
 
-// the layers this file serves or forwards, whatever the band count
-static int band_layer_ok(const dcll_conv_desc *d, const char *who)
-{
-    int rc = check_desc(d);
-    if (rc) return rc;
-    if (!plain_conv(d)) return fail(DCLL_ERR_UNSUPPORTED, "plain convolutions only: stride, dilation and groups must be 1", who);
-    if (d->c_out > BAND_MAX_COUT) return fail(DCLL_ERR_UNSUPPORTED, "c_out <= 64 (two 32-row MFMA tiles of output channels)", who);
-    if (d->kh > BAND_MAX_K || d->kw > BAND_MAX_K) return fail(DCLL_ERR_UNSUPPORTED, "kernels up to 16x16", who);
-    return DCLL_OK;
-}
 // n bands fit: one band = the one-workgroup kernels' own predicate; more = the largest band's set within the LDS
 static bool band_fits(const dcll_conv_desc *d, int n)
 {
     if (n == 1) return dcll_conv_lif_sequence_wide_lds(d) > 0;
-    return band_floats_max(d, n) * 4 <= BAND_LDS_MAX;
+    return band_floats_max(d, n) * 4 <= ANY_LDS_MAX;
 }
 // pixel tiles of the largest band
 static int band_tiles_max(const dcll_conv_desc *d, int NB)
@@ -172,7 +127,7 @@ static int band_rule(const dcll_conv_desc *d, int B)
     conv_shape(d, &ch, &cw, &ph, &pw);
     for (int n = 1; n <= ph; ++n) {
         if (!band_fits(d, n)) continue;
-        if (best && (long)B * n > BAND_CUS) break;
+        if (best && (long)B * n > ANY_CUS) break;
         best = n;
         const int tiles = band_tiles_max(d, n);
         if (n == 1 ? band_mt(d) * ((tiles + BAND_NW - 1) / BAND_NW) == 1 : tiles <= 1) break;
@@ -183,7 +138,7 @@ static int band_rule(const dcll_conv_desc *d, int B)
 // the band count a call runs (0: refused, rc and the message set)
 static int band_count(const dcll_conv_desc *d, int B, int bands, const char *who, int *rc)
 {
-    *rc = band_layer_ok(d, who);
+    *rc = any_layer_ok(d, BAND_MAX_COUT, who);
     if (*rc) return 0;
     if (bands < 0) {
         *rc = fail(DCLL_ERR_INVALID, "negative band count", who);
@@ -233,34 +188,8 @@ extern "C" int64_t dcll_conv_lif_sequence_bands_scratch(const dcll_conv_desc *d,
 {
     int rc;
     if (!band_count(d, B, 0, "dcll_conv_lif_sequence_bands_scratch", &rc) || B < 0) return 0;
-    return band_steps(d) * 64 * band_mt(d) + 2L * B * d->c_in * d->h * d->w;
+    return any_chain_steps(d) * 64 * band_mt(d) + 2L * B * d->c_in * d->h * d->w;
 }
-
-// W (c_out, c_in, kh, kw) -> wperm[m][mt][lane]: link 2 m + h of channel co = 32 mt + (lane & 31), h = lane >> 5; 0 beyond
-// c_out / the chain
-__global__ void k_seq_band_wprep(const float *__restrict__ W, float *__restrict__ wperm, int c_in, int c_out, int kh, int kw,
-                                 int npair, int nsteps, int MT)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nsteps * 64 * MT) return;
-    const int lane = i & 63, u = i >> 6, mt = u % MT, m = u / MT, co = 32 * mt + (lane & 31), h = lane >> 5, KK = kh * kw;
-    int ci, tap;
-    if (m < npair) {
-        ci = 2 * (m / KK) + h;
-        tap = m % KK;
-    } else {
-        ci = c_in - 1;
-        tap = 2 * (m - npair) + h;
-    }
-    wperm[i] = (co < c_out && tap < KK) ? W[((long)co * c_in + ci) * KK + tap] : 0.0f;
-}
-
-template <int NM>
-struct band_acc {
-    f32x16 t[NM];
-};
-
-__device__ __forceinline__ any_div band_div(int d) { return any_div{d > 1 ? (uint32_t)(((1ull << 32) + d - 1) / d) : 0u, d}; }
 
 template <int MT, bool R, bool WLDS>
 __global__ __launch_bounds__(BAND_THREADS) void k_lif_seq_band(const band_geom g, const uint32_t *__restrict__ spk_in,
@@ -283,7 +212,7 @@ __global__ __launch_bounds__(BAND_THREADS) void k_lif_seq_band(const band_geom g
     const int HW = g.h * g.w, NIN = g.c_in * HW, NV = g.c_out * g.CP;
     const int HBW = L.HB * g.w, NINb = g.c_in * HBW, NVb = g.c_out * L.CPb, NTL = (L.CPb + 31) >> 5;
     const int pg0 = r.I0 * g.w, cp0 = r.C0 * g.cw;             // first held input pixel, first conv pixel, of the sample's planes
-    const any_div dHBW = band_div(HBW), dCPb = band_div(L.CPb);
+    const any_div dHBW = make_div(HBW), dCPb = make_div(L.CPb);
 
     // position of held input element i (channel ci, band pixel p = (y - I0) w + x) in img
     auto img_at = [&](int i, int &ci, int &p) -> int {
@@ -291,6 +220,12 @@ __global__ __launch_bounds__(BAND_THREADS) void k_lif_seq_band(const band_geom g
         p = i - ci * HBW;
         const int yl = fdiv(p, g.dW), x = p - yl * g.w;
         return ci * L.CHS + (r.I0 + yl + g.pad_h - r.C0) * g.WP + x + g.pad_w;
+    };
+
+    // conv element i (channel co, band pixel) -> its pixel in the sample's conv plane
+    auto conv_at = [&](int i, int &co) -> int {
+        co = fdiv(i, dCPb);
+        return cp0 + i - co * L.CPb;
     };
 
     // ---- prologue: the band's state (from the snapshot) and constants on chip
@@ -305,12 +240,11 @@ __global__ __launch_bounds__(BAND_THREADS) void k_lif_seq_band(const band_geom g
     }
     if (R)
         for (int i = tid; i < NVb; i += BAND_THREADS) {
-            const int co = fdiv(i, dCPb), pl = i - co * L.CPb;
-            arps[i] = arp_g[b * NV + co * g.CP + cp0 + pl];
+            int co;
+            const int cp = conv_at(i, co);
+            arps[i] = arp_g[b * NV + co * g.CP + cp];
         }
-    for (int i = tid; i < 4 * g.c_in; i += BAND_THREADS) taus[i] = tau4[i];
-    if (tid < 32 * MT) sb[tid] = (bias && tid < g.c_out) ? bias[tid] : 0.0f;
-    for (int i = tid; i < (WLDS ? g.nsteps : g.nwl) * 64 * MT; i += BAND_THREADS) wl[i] = wperm[i];
+    any_consts_to_lds<MT, WLDS, BAND_THREADS>(taus, sb, wl, tau4, bias, wperm, g.c_in, g.c_out, g.nsteps, g.nwl, tid);
     __syncthreads();
 
     // the trace update of held input element i at step t (eps0 in e0s, eps1 in place in img)
@@ -324,85 +258,11 @@ __global__ __launch_bounds__(BAND_THREADS) void k_lif_seq_band(const band_geom g
         img[q] = e1;
     };
 
-    // NM chains (M tiles mt0 .. mt0 + NM - 1) of pixel tile tl of the band: one B operand read per step for all of them
+    // NM chains (M tiles mt0 .. mt0 + NM - 1) of pixel tile tl of the band
     auto chain = [&](auto nm_, int tl, int mt0) {
-        constexpr int NM = decltype(nm_)::value;
         const int pix = tl * 32 + j, pc = pix < L.CPb ? pix : L.CPb - 1, y = fdiv(pc, g.dCW), x = pc - y * g.cw;
-        const int base0 = y * g.WP + x;
-        const float *bp = img + base0 + hh * L.CHS;
-        band_acc<NM> acc;
-#pragma unroll
-        for (int n = 0; n < NM; ++n)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc.t[n][q] = sb[32 * (mt0 + n) + (q & 3) + 8 * (q >> 2) + 4 * hh];
-        auto wa = [&](int m, int n) -> float {
-            const int o = (m * MT + mt0 + n) * 64 + lane;
-            if constexpr (WLDS) return wl[o];
-            else return m < g.nwl ? wl[o] : wperm[o];
-        };
-        int m = 0, off = 0, kx = 0, ky = 0;
-        // the weights of eight steps are requested a whole batch ahead of their use: the streamed ones come from L2, and a wave
-        // that waited for every batch in turn spent its chain on that latency (16 steps in flight per M tile)
-        float a[NM][8], an[NM][8];
-        auto fetch = [&](float (&dst)[NM][8], int m0) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int mu = m0 + u < g.npair ? m0 + u : g.npair - 1;
-#pragma unroll
-                for (int n = 0; n < NM; ++n) dst[n][u] = wa(mu, n);
-            }
-        };
-        if (g.npair > 0) fetch(an, 0);
-        for (; m < g.npair; m += 8) {       // (cp, ky, kx): both channels of the pair at one wave-uniform offset
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-#pragma unroll
-                for (int n = 0; n < NM; ++n) a[n][u] = an[n][u];
-            if (m + 8 < g.npair) fetch(an, m + 8);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                if (m + u < g.npair) {
-                    const float bv = bp[off];
-#pragma unroll
-                    for (int n = 0; n < NM; ++n) acc.t[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[n][u], bv, acc.t[n], 0, 0, 0);
-                    ++off;
-                    if (++kx == g.kw) {
-                        kx = 0;
-                        off += g.WP - g.kw;
-                        if (++ky == g.kh) {
-                            ky = 0;
-                            off += 2 * L.CHS - g.kh * g.WP;
-                        }
-                    }
-                }
-            }
-        }
-        m = g.npair;
-        if (g.c_in & 1) {                   // the last channel alone: taps (2 q, 2 q + 1), tap KK (odd KK) is the zero link
-            const float *cb = img + (g.c_in - 1) * L.CHS + base0;
-            const int KK = g.kh * g.kw;
-            int tap = hh, tkx = hh, tky = 0;
-            while (tkx >= g.kw) { tkx -= g.kw; ++tky; }
-            for (; m < g.nsteps; ++m) {
-                const float bv = tap < KK ? cb[tky * g.WP + tkx] : 0.0f;
-#pragma unroll
-                for (int n = 0; n < NM; ++n) acc.t[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(wa(m, n), bv, acc.t[n], 0, 0, 0);
-                tap += 2;
-                tkx += 2;
-                while (tkx >= g.kw) { tkx -= g.kw; ++tky; }
-            }
-        }
-        return acc;
-    };
-    auto to_vpl = [&](const f32x16 &acc, int tl, int mt) {
-        const int pix = tl * 32 + j;
-        if (pix < L.CPb) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int co = 32 * mt + (q & 3) + 8 * (q >> 2) + 4 * hh;
-                if (co < g.c_out) vpl[co * L.CPb + pix] = acc[q];
-            }
-        }
+        return any_chain<decltype(nm_)::value, MT, WLDS>(img, g.WP, L.CHS, y * g.WP + x, sb, wl, wperm, g.nwl, g.npair, g.nsteps,
+                                                         g.c_in, g.kh, g.kw, lane, hh, mt0);
     };
 
     // pooling pass of step t over vpl: a half wave = the 32 pixels of one spike word of one channel, over the words that hold a
@@ -451,36 +311,20 @@ __global__ __launch_bounds__(BAND_THREADS) void k_lif_seq_band(const band_geom g
         // ---- phase B: the chains -> vpl
         if (MT == 1 || NTL >= BAND_NW) {
             for (int tl = wv; tl < NTL; tl += BAND_NW) {
-                const band_acc<MT> acc = chain(std::integral_constant<int, MT>{}, tl, 0);
+                const any_acc<MT> acc = chain(std::integral_constant<int, MT>{}, tl, 0);
 #pragma unroll
-                for (int mt = 0; mt < MT; ++mt) to_vpl(acc.t[mt], tl, mt);
+                for (int mt = 0; mt < MT; ++mt) any_to_vpl(acc.t[mt], vpl, L.CPb, g.c_out, tl * 32 + j, mt, hh);
             }
         } else {
             for (int u = wv; u < NTL * MT; u += BAND_NW) {       // few tiles: one (tile, M tile) per wave
                 const int tl = u / MT, mt = u - tl * MT;
-                const band_acc<1> acc = chain(std::integral_constant<int, 1>{}, tl, mt);
-                to_vpl(acc.t[0], tl, mt);
+                const any_acc<1> acc = chain(std::integral_constant<int, 1>{}, tl, mt);
+                any_to_vpl(acc.t[0], vpl, L.CPb, g.c_out, tl * 32 + j, mt, hh);
             }
         }
         __syncthreads();
         // ---- phase C: refractory update on the v plane, v_out
-        if (R || v_out) {
-            for (int i = tid; i < NVb; i += BAND_THREADS) {
-                float v = vpl[i];
-                if (R) {
-                    float a = arps[i];
-                    bool s;
-                    v = refractory(v, a, alpharp, wrp, s);
-                    arps[i] = a;
-                    vpl[i] = v;
-                }
-                if (v_out) {
-                    const int co = fdiv(i, dCPb), pl = i - co * L.CPb;
-                    v_out[(ob + co) * g.CP + cp0 + pl] = v;
-                }
-            }
-            __syncthreads();
-        }
+        any_phase_c<R, BAND_THREADS>(vpl, arps, NVb, v_out, ob, g.CP, tid, alpharp, wrp, conv_at);
     }
     // ---- last step's pooled outputs; the owned state back to HBM
     pool_pass(T - 1);
@@ -495,37 +339,28 @@ __global__ __launch_bounds__(BAND_THREADS) void k_lif_seq_band(const band_geom g
     }
     if (R)
         for (int i = tid; i < NVb; i += BAND_THREADS) {
-            const int co = fdiv(i, dCPb), pl = i - co * L.CPb;
-            arp_g[b * NV + co * g.CP + cp0 + pl] = arps[i];
+            int co;
+            const int cp = conv_at(i, co);
+            arp_g[b * NV + co * g.CP + cp] = arps[i];
         }
 }
 
 // the LDS reservation, then the weight permutation, the snapshot, the zero fill, then the kernel: an error return never follows
 // a launch of the layer kernel
 template <int MT, bool R, bool WLDS>
-static int launch_band(const band_geom &g, size_t lds_bytes, bool shared_words, const uint32_t *spk_in, const float *W, float *scratch,
-                       const float *b, const float *tau4, float *eps0, float *eps1, float *arp, uint32_t *spk_out, float *pv_out,
-                       float *v_out, int T, int B, float alpharp, float wrp, hipStream_t st, const char *name)
+static int launch_band(const dcll_conv_desc *d, const band_geom &g, size_t lds_bytes, bool shared_words, const uint32_t *spk_in,
+                       const float *W, float *scratch, const float *b, const float *tau4, float *eps0, float *eps1, float *arp,
+                       uint32_t *spk_out, float *pv_out, float *v_out, int T, int B, float alpharp, float wrp, hipStream_t st, const char *name)
 {
     if (hipFuncSetAttribute((const void *)k_lif_seq_band<MT, R, WLDS>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)lds_bytes) != hipSuccess) {
         (void)hipGetLastError();
         return fail(DCLL_ERR_LAUNCH, "k_lif_seq_band: cannot reserve its LDS");
     }
-    const int n = g.nsteps * 64 * MT;
-    const size_t nin = (size_t)B * g.c_in * g.h * g.w;
-    float *snap0 = scratch + n, *snap1 = snap0 + nin;
-    hipLaunchKernelGGL(k_seq_band_wprep, dim3((n + 255) / 256), dim3(256), 0, st, W, scratch, g.c_in, g.c_out, g.kh, g.kw, g.npair,
-                       g.nsteps, MT);
-    hipError_t e = hipGetLastError();           // (not in the launch log, like k_seq_wide_wprep)
-    if (e == hipSuccess) e = hipMemcpyAsync(snap0, eps0, nin * sizeof(float), hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(snap1, eps1, nin * sizeof(float), hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess && shared_words && spk_out)
-        e = hipMemsetAsync(spk_out, 0, (size_t)T * B * g.c_out * g.ow * sizeof(uint32_t), st);
-    if (e != hipSuccess) {
-        snprintf(dcll_err_buf(), DCLL_ERR_LEN, "k_lif_seq_band (weight permutation, state snapshot, zero fill): %s", hipGetErrorString(e));
-        return DCLL_ERR_LAUNCH;
-    }
+    float *snap0, *snap1;
+    const int rc = seq_split_prepare(d, W, scratch, MT, eps0, eps1, spk_out, (size_t)T * B * g.c_out * g.ow, shared_words, B, st,
+                                     "k_lif_seq_band", &snap0, &snap1);
+    if (rc) return rc;
     hipLaunchKernelGGL((k_lif_seq_band<MT, R, WLDS>), dim3((unsigned)((long)B * g.NB)), dim3(BAND_THREADS), lds_bytes, st, g, spk_in,
                        scratch, b, tau4, snap0, snap1, eps0, eps1, arp, spk_out, pv_out, v_out, T, B, alpharp, wrp);
     HIP_CHECK_LAUNCH(name);
@@ -558,8 +393,8 @@ extern "C" int dcll_conv_lif_sequence_bands(const dcll_conv_desc *d, const uint3
     conv_shape(d, &g.ch, &g.cw, &g.ph, &g.pw);
     g.CP = g.ch * g.cw;
     g.PP = g.ph * g.pw;
-    g.npair = (d->c_in / 2) * d->kh * d->kw;
-    g.nsteps = (int)band_steps(d);
+    g.npair = (int)any_chain_pairs(d);
+    g.nsteps = (int)any_chain_steps(d);
     g.iw = (d->h * d->w + 31) / 32;
     g.ow = (g.PP + 31) / 32;
     g.NB = NB;
@@ -575,35 +410,16 @@ extern "C" int dcll_conv_lif_sequence_bands(const dcll_conv_desc *d, const uint3
         if (L.end > base) base = L.end;
         if (k && (r.P0 * g.pw) % 32) shared_words = true;
     }
-    if (base * 4 > BAND_LDS_MAX) return fail(DCLL_ERR_LAUNCH, "a band's LDS beyond the limit", who);
+    if (base * 4 > ANY_LDS_MAX) return fail(DCLL_ERR_LAUNCH, "a band's LDS beyond the limit", who);
     g.o_w = (int)base;
-    // weights that do not fit as a whole: a grid of more than one workgroup per CU keeps half of the LDS free so that two bands
-    // share a CU (the rule of k_lif_seq_any)
-    const long per = 64 * MT;
-    const bool whole = (base + (long)g.nsteps * per) * 4 <= BAND_LDS_MAX;
-    const long budget = (!whole && (long)B * NB > BAND_CUS && base * 4 * 2 <= BAND_LDS_MAX) ? BAND_LDS_MAX / 2 : BAND_LDS_MAX;
-    const long room = (budget / 4 - base) / per;
-    g.nwl = (int)(room < g.nsteps ? room : g.nsteps);
+    g.nwl = seq_weight_room(base, g.nsteps, MT, (long)B * NB);
     const bool wlds = g.nwl == g.nsteps;
-    const size_t lds_bytes = (size_t)(base + (long)g.nwl * per) * 4;
+    const size_t lds_bytes = (size_t)(base + (long)g.nwl * 64 * MT) * 4;
 
     // launch-log names: k_lif_seq_band<M tiles, refractory, weights in LDS>
 #define DCLL_BAND(M_, R_, L_)                                                                                                   \
-    return launch_band<M_, R_, L_>(g, lds_bytes, shared_words, spk_in, W, scratch, b, tau4, eps0, eps1, arp, spk_out, pv_out,   \
+    return launch_band<M_, R_, L_>(d, g, lds_bytes, shared_words, spk_in, W, scratch, b, tau4, eps0, eps1, arp, spk_out, pv_out,  \
                                    v_out, T, B, d->alpharp, d->wrp, st, "k_lif_seq_band<" #M_ "," #R_ "," #L_ ">")
-    if (MT == 1) {
-        if (d->refractory) {
-            if (wlds) DCLL_BAND(1, 1, 1);
-            DCLL_BAND(1, 1, 0);
-        }
-        if (wlds) DCLL_BAND(1, 0, 1);
-        DCLL_BAND(1, 0, 0);
-    }
-    if (d->refractory) {
-        if (wlds) DCLL_BAND(2, 1, 1);
-        DCLL_BAND(2, 1, 0);
-    }
-    if (wlds) DCLL_BAND(2, 0, 1);
-    DCLL_BAND(2, 0, 0);
+    DCLL_SEQ_SPLIT_DISPATCH(DCLL_BAND, MT, d->refractory, wlds);
 #undef DCLL_BAND
 }

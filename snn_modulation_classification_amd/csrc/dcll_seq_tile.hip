@@ -8,15 +8,10 @@
 // bit-identical to k_lif_seq_band / k_lif_seq_wide / k_lif_seq_any wherever those serve the layer.
 // tiles_x = 1 hands the call to dcll_conv_lif_sequence_bands unchanged (bands = tiles_y).
 //
-// Tile plan: the product of two 1-D band plans (band_plan() is the ONE statement of it; tests/seq_tile_cases.py restates it).
-// Tile (a, b) of NY x NX takes its rows from band_plan(a, NY, h, kh, pad_h, pool_h, ch, ph) and its columns from
-// band_plan(b, NX, w, kw, pad_w, pool_w, cw, pw):
-//   owned pooled pixels [P0, P1): [k p / N, (k + 1) p / N)                                                     (floor)
-//   conv pixels  [C0, C1): the union of those pooling windows clipped to the conv plane; the last tile of a direction also takes
-//                the conv pixels behind the last window (floor-mode pooling leaves such pixels).  A partition.
-//   input pixels held [I0, I1) = [C0 - pad, C1 - pad + k - 1) clipped to the image; outside the image is the zero padding
-//   input pixels owned [O0, O1) = [I0(k), I0(k + 1)) (last: up to the image's end): the one tile that writes an element's final
-//                eps0 / eps1
+// Tile plan: the product of two 1-D band plans (band_plan() of dcll_any_shared.h; tests/seq_tile_cases.py restates it).  Tile (a, b)
+// of NY x NX takes its rows from band_plan(a, NY, h, kh, pad_h, pool_h, ch, ph) and its columns from
+// band_plan(b, NX, w, kw, pad_w, pool_w, cw, pw): owned pooled pixels [P0, P1), conv pixels [C0, C1), held input pixels [I0, I1),
+// owned input pixels [O0, O1) in each direction.
 // arp, v_out of a conv pixel and pv, spike bit of a pooled pixel have one owner by construction.
 //
 // LDS of a tile (floats; tile_floats() is the ONE statement of it, exported as dcll_conv_lif_sequence_tiles_lds for the largest
@@ -34,42 +29,16 @@
 // a word wholly inside one segment is stored, every other word is ORed into (an ordinary vector atomicOr) after the launcher
 // has zero-filled spk_out on the stream.  OR is commutative: the bits do not depend on the order.
 //
-// Arithmetic, weight permutation, weight prefetch, work split and phases are k_lif_seq_band's, restated here: chain of output
-// (co, y, x) from bias[co] over the links (cp, ky, kx, h), one v_mfma_f32_32x32x2_f32 per two consecutive links; phases
-// A traces + pooling pass of t - 1 | B chains -> vpl | C refractory update + v_out, a barrier behind each.  The units of a tile
-// are (32-pixel tile of the tile's flattened conv pixels, M tile): with at least 8 pixel tiles a wave runs all MT chains of a
-// pixel tile on one B read; with fewer, units go one per wave.
+// Arithmetic, weight prefetch, work split and phases are k_lif_seq_band's.  Chain length, weight permutation, weights-in-LDS budget,
+// the launch prologue and the device code shared with k_lif_seq_band (chain, to_vpl, phase C, constant prologue) come from
+// dcll_any_shared.h.  The units of a tile are (32-pixel tile of the tile's flattened conv pixels, M tile): with at least 8 pixel
+// tiles a wave runs all MT chains of a pixel tile on one B read; with fewer, units go one per wave.
 #include <vector>
 
-#include "dcll_internal.h"
+#include "dcll_any_shared.h"
 
 constexpr int TILE_THREADS = 512, TILE_NW = TILE_THREADS / 64;
-constexpr long TILE_LDS_MAX = 160 * 1024;
-constexpr int TILE_MAX_K = 16, TILE_MAX_COUT = 64;
-constexpr int TILE_CUS = 256;       // the half-LDS rule's device: an MI355X
-
-struct band_rows {
-    int P0, P1, C0, C1, I0, I1, O0, O1;
-};
-
-// the 1-D plan: pixels of part k of NB (1 <= NB <= ph) in one direction — dcll_seq_band.hip's, restated
-__host__ __device__ static inline band_rows band_plan(int k, int NB, int h, int kh, int pad_h, int pool_h, int ch, int ph)
-{
-    const int pph = (pool_h - 1) / 2;
-    band_rows r;
-    r.P0 = (int)((long)k * ph / NB);
-    r.P1 = (int)((long)(k + 1) * ph / NB);
-    const int c0 = r.P0 * pool_h - pph, c1 = r.P1 * pool_h - pph;   // first conv pixel of the windows of pooled pixels P0, P1
-    r.C0 = c0 < 0 ? 0 : c0;
-    r.C1 = (k == NB - 1) ? ch : (c1 < 0 ? 0 : c1);
-    const int i0 = r.C0 - pad_h, i1 = r.C1 - pad_h + kh - 1;
-    r.I0 = i0 < 0 ? 0 : (i0 > h ? h : i0);
-    r.I1 = i1 < 0 ? 0 : (i1 > h ? h : i1);
-    const int o1 = r.C1 - pad_h;                                    // = I0 of part k + 1
-    r.O0 = r.I0;
-    r.O1 = (k == NB - 1) ? h : (o1 < 0 ? 0 : (o1 > h ? h : o1));
-    return r;
-}
+constexpr int TILE_MAX_COUT = 64;
 
 struct tile_geom {
     int c_in, c_out, h, w, kh, kw, pad_h, pad_w, pool_h, pool_w;
@@ -152,23 +121,8 @@ static long tile_floats_max(const dcll_conv_desc *d, int NY, int NX, long *held 
     if (held) *held = ay.held * ax.held;
     return m;
 }
-static inline long tile_steps(const dcll_conv_desc *d)
-{
-    const long KK = (long)d->kh * d->kw;
-    return (d->c_in / 2) * KK + ((d->c_in & 1) ? (KK + 1) / 2 : 0);
-}
 
-// the layers this file serves or forwards, whatever the plan
-static int tile_layer_ok(const dcll_conv_desc *d, const char *who)
-{
-    int rc = check_desc(d);
-    if (rc) return rc;
-    if (!plain_conv(d)) return fail(DCLL_ERR_UNSUPPORTED, "plain convolutions only: stride, dilation and groups must be 1", who);
-    if (d->c_out > TILE_MAX_COUT) return fail(DCLL_ERR_UNSUPPORTED, "c_out <= 64 (two 32-row MFMA tiles of output channels)", who);
-    if (d->kh > TILE_MAX_K || d->kw > TILE_MAX_K) return fail(DCLL_ERR_UNSUPPORTED, "kernels up to 16x16", who);
-    return DCLL_OK;
-}
-static bool tile_fits(const dcll_conv_desc *d, int NY, int NX) { return tile_floats_max(d, NY, NX) * 4 <= TILE_LDS_MAX; }
+static bool tile_fits(const dcll_conv_desc *d, int NY, int NX) { return tile_floats_max(d, NY, NX) * 4 <= ANY_LDS_MAX; }
 
 // The (0, 0) rule where no band count serves the layer: the fitting (NY, NX), NX >= 2, with the fewest tiles; ties go to the
 // smallest sum of held input elements over all tiles (the least recomputed trace work), then to the smaller NX.  DERIVED FROM THE
@@ -182,7 +136,7 @@ static bool tile_rule(const dcll_conv_desc *d, int *NY, int *NX)
         for (int nx = 2; nx <= pw && nx <= n; ++nx) {
             if (n % nx || n / nx > ph) continue;
             long held;
-            if (tile_floats_max(d, (int)(n / nx), nx, &held) * 4 > TILE_LDS_MAX) continue;
+            if (tile_floats_max(d, (int)(n / nx), nx, &held) * 4 > ANY_LDS_MAX) continue;
             if (best < 0 || held < best) {
                 best = held;
                 *NY = (int)(n / nx);
@@ -198,7 +152,7 @@ static bool tile_rule(const dcll_conv_desc *d, int *NY, int *NX)
 // dcll_conv_lif_sequence_bands with bands = *bands
 static int tile_count(const dcll_conv_desc *d, int B, int ty, int tx, const char *who, int *rc, int *NY, int *NX, int *bands)
 {
-    *rc = tile_layer_ok(d, who);
+    *rc = any_layer_ok(d, TILE_MAX_COUT, who);
     if (*rc) return 0;
     if (ty < 0 || tx < 0) {
         *rc = fail(DCLL_ERR_INVALID, "negative tile count", who);
@@ -265,34 +219,8 @@ extern "C" int64_t dcll_conv_lif_sequence_tiles_scratch(const dcll_conv_desc *d,
 {
     int rc, NY = 0, NX = 0, bands = 0;
     if (!tile_count(d, B, 0, 0, "dcll_conv_lif_sequence_tiles_scratch", &rc, &NY, &NX, &bands) || B < 0) return 0;
-    return tile_steps(d) * 64 * tile_mt(d) + 2L * B * d->c_in * d->h * d->w;
+    return any_chain_steps(d) * 64 * tile_mt(d) + 2L * B * d->c_in * d->h * d->w;
 }
-
-// W (c_out, c_in, kh, kw) -> wperm[m][mt][lane]: link 2 m + h of channel co = 32 mt + (lane & 31), h = lane >> 5; 0 beyond
-// c_out / the chain
-__global__ void k_seq_tile_wprep(const float *__restrict__ W, float *__restrict__ wperm, int c_in, int c_out, int kh, int kw,
-                                 int npair, int nsteps, int MT)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nsteps * 64 * MT) return;
-    const int lane = i & 63, u = i >> 6, mt = u % MT, m = u / MT, co = 32 * mt + (lane & 31), h = lane >> 5, KK = kh * kw;
-    int ci, tap;
-    if (m < npair) {
-        ci = 2 * (m / KK) + h;
-        tap = m % KK;
-    } else {
-        ci = c_in - 1;
-        tap = 2 * (m - npair) + h;
-    }
-    wperm[i] = (co < c_out && tap < KK) ? W[((long)co * c_in + ci) * KK + tap] : 0.0f;
-}
-
-template <int NM>
-struct tile_acc {
-    f32x16 t[NM];
-};
-
-__device__ __forceinline__ any_div tile_div(int d) { return any_div{d > 1 ? (uint32_t)(((1ull << 32) + d - 1) / d) : 0u, d}; }
 
 template <int MT, bool R, bool WLDS>
 __global__ __launch_bounds__(TILE_THREADS) void k_lif_seq_tile(const tile_geom g, const uint32_t *__restrict__ spk_in,
@@ -317,7 +245,7 @@ __global__ __launch_bounds__(TILE_THREADS) void k_lif_seq_tile(const tile_geom g
     const int HP = L.HR * L.HC, NINt = g.c_in * HP, NVt = g.c_out * L.CPt, NTL = (L.CPt + 31) >> 5;
     const int q0 = (ry.I0 + g.pad_h - ry.C0) * L.CB + rx.I0 + g.pad_w - rx.C0;  // the first held input pixel in a channel of img
     const int pg0 = ry.I0 * g.w + rx.I0, cp0 = ry.C0 * g.cw + rx.C0;          // ... and the first conv pixel, in the sample's planes
-    const any_div dHP = tile_div(HP), dHC = tile_div(L.HC), dCPt = tile_div(L.CPt), dCC = tile_div(L.CC);
+    const any_div dHP = make_div(HP), dHC = make_div(L.HC), dCPt = make_div(L.CPt), dCC = make_div(L.CC);
 
     // held input element i (channel ci, tile pixel (yl, xl)) -> its position in img; pg: its pixel in the sample's plane
     auto img_at = [&](int i, int &ci, int &yl, int &xl, int &pg) -> int {
@@ -351,9 +279,7 @@ __global__ __launch_bounds__(TILE_THREADS) void k_lif_seq_tile(const tile_geom g
             const int cp = conv_at(i, co);
             arps[i] = arp_g[b * NV + co * g.CP + cp];
         }
-    for (int i = tid; i < 4 * g.c_in; i += TILE_THREADS) taus[i] = tau4[i];
-    if (tid < 32 * MT) sb[tid] = (bias && tid < g.c_out) ? bias[tid] : 0.0f;
-    for (int i = tid; i < (WLDS ? g.nsteps : g.nwl) * 64 * MT; i += TILE_THREADS) wl[i] = wperm[i];
+    any_consts_to_lds<MT, WLDS, TILE_THREADS>(taus, sb, wl, tau4, bias, wperm, g.c_in, g.c_out, g.nsteps, g.nwl, tid);
     __syncthreads();
 
     // the trace update of held input element i at step t (eps0 in e0s, eps1 in place in img)
@@ -367,84 +293,11 @@ __global__ __launch_bounds__(TILE_THREADS) void k_lif_seq_tile(const tile_geom g
         img[q] = e1;
     };
 
-    // NM chains (M tiles mt0 .. mt0 + NM - 1) of pixel tile tl of the tile: one B operand read per step for all of them
+    // NM chains (M tiles mt0 .. mt0 + NM - 1) of pixel tile tl of the tile
     auto chain = [&](auto nm_, int tl, int mt0) {
-        constexpr int NM = decltype(nm_)::value;
         const int pix = tl * 32 + j, pc = pix < L.CPt ? pix : L.CPt - 1, y = fdiv(pc, dCC), x = pc - y * L.CC;
-        const int base0 = y * L.CB + x;
-        const float *bp = img + base0 + hh * L.CHS;
-        tile_acc<NM> acc;
-#pragma unroll
-        for (int n = 0; n < NM; ++n)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc.t[n][q] = sb[32 * (mt0 + n) + (q & 3) + 8 * (q >> 2) + 4 * hh];
-        auto wa = [&](int m, int n) -> float {
-            const int o = (m * MT + mt0 + n) * 64 + lane;
-            if constexpr (WLDS) return wl[o];
-            else return m < g.nwl ? wl[o] : wperm[o];
-        };
-        int m = 0, off = 0, kx = 0, ky = 0;
-        // the weights of eight steps are requested a whole batch ahead of their use (k_lif_seq_band's prefetch)
-        float a[NM][8], an[NM][8];
-        auto fetch = [&](float (&dst)[NM][8], int m0) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int mu = m0 + u < g.npair ? m0 + u : g.npair - 1;
-#pragma unroll
-                for (int n = 0; n < NM; ++n) dst[n][u] = wa(mu, n);
-            }
-        };
-        if (g.npair > 0) fetch(an, 0);
-        for (; m < g.npair; m += 8) {       // (cp, ky, kx): both channels of the pair at one wave-uniform offset
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-#pragma unroll
-                for (int n = 0; n < NM; ++n) a[n][u] = an[n][u];
-            if (m + 8 < g.npair) fetch(an, m + 8);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                if (m + u < g.npair) {
-                    const float bv = bp[off];
-#pragma unroll
-                    for (int n = 0; n < NM; ++n) acc.t[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[n][u], bv, acc.t[n], 0, 0, 0);
-                    ++off;
-                    if (++kx == g.kw) {
-                        kx = 0;
-                        off += L.CB - g.kw;
-                        if (++ky == g.kh) {
-                            ky = 0;
-                            off += 2 * L.CHS - g.kh * L.CB;
-                        }
-                    }
-                }
-            }
-        }
-        m = g.npair;
-        if (g.c_in & 1) {                   // the last channel alone: taps (2 q, 2 q + 1), tap KK (odd KK) is the zero link
-            const float *cb = img + (g.c_in - 1) * L.CHS + base0;
-            const int KK = g.kh * g.kw;
-            int tap = hh, tkx = hh, tky = 0;
-            while (tkx >= g.kw) { tkx -= g.kw; ++tky; }
-            for (; m < g.nsteps; ++m) {
-                const float bv = tap < KK ? cb[tky * L.CB + tkx] : 0.0f;
-#pragma unroll
-                for (int n = 0; n < NM; ++n) acc.t[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(wa(m, n), bv, acc.t[n], 0, 0, 0);
-                tap += 2;
-                tkx += 2;
-                while (tkx >= g.kw) { tkx -= g.kw; ++tky; }
-            }
-        }
-        return acc;
-    };
-    auto to_vpl = [&](const f32x16 &acc, int tl, int mt) {
-        const int pix = tl * 32 + j;
-        if (pix < L.CPt) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int co = 32 * mt + (q & 3) + 8 * (q >> 2) + 4 * hh;
-                if (co < g.c_out) vpl[co * L.CPt + pix] = acc[q];
-            }
-        }
+        return any_chain<decltype(nm_)::value, MT, WLDS>(img, L.CB, L.CHS, y * L.CB + x, sb, wl, wperm, g.nwl, g.npair, g.nsteps,
+                                                         g.c_in, g.kh, g.kw, lane, hh, mt0);
     };
 
     // pooling pass of step t over vpl: a half wave = the 32 pixels of one spike word of one channel.  The tile's pooled pixels are
@@ -495,37 +348,20 @@ __global__ __launch_bounds__(TILE_THREADS) void k_lif_seq_tile(const tile_geom g
         // ---- phase B: the chains -> vpl
         if (MT == 1 || NTL >= TILE_NW) {
             for (int tl = wv; tl < NTL; tl += TILE_NW) {
-                const tile_acc<MT> acc = chain(std::integral_constant<int, MT>{}, tl, 0);
+                const any_acc<MT> acc = chain(std::integral_constant<int, MT>{}, tl, 0);
 #pragma unroll
-                for (int mt = 0; mt < MT; ++mt) to_vpl(acc.t[mt], tl, mt);
+                for (int mt = 0; mt < MT; ++mt) any_to_vpl(acc.t[mt], vpl, L.CPt, g.c_out, tl * 32 + j, mt, hh);
             }
         } else {
             for (int u = wv; u < NTL * MT; u += TILE_NW) {       // few pixel tiles: one (pixel tile, M tile) per wave
                 const int tl = u / MT, mt = u - tl * MT;
-                const tile_acc<1> acc = chain(std::integral_constant<int, 1>{}, tl, mt);
-                to_vpl(acc.t[0], tl, mt);
+                const any_acc<1> acc = chain(std::integral_constant<int, 1>{}, tl, mt);
+                any_to_vpl(acc.t[0], vpl, L.CPt, g.c_out, tl * 32 + j, mt, hh);
             }
         }
         __syncthreads();
         // ---- phase C: refractory update on the v plane, v_out
-        if (R || v_out) {
-            for (int i = tid; i < NVt; i += TILE_THREADS) {
-                float v = vpl[i];
-                if (R) {
-                    float a = arps[i];
-                    bool s;
-                    v = refractory(v, a, alpharp, wrp, s);
-                    arps[i] = a;
-                    vpl[i] = v;
-                }
-                if (v_out) {
-                    int co;
-                    const int cp = conv_at(i, co);
-                    v_out[(ob + co) * g.CP + cp] = v;
-                }
-            }
-            __syncthreads();
-        }
+        any_phase_c<R, TILE_THREADS>(vpl, arps, NVt, v_out, ob, g.CP, tid, alpharp, wrp, conv_at);
     }
     // ---- last step's pooled outputs; the owned state back to HBM
     pool_pass(T - 1);
@@ -549,29 +385,19 @@ __global__ __launch_bounds__(TILE_THREADS) void k_lif_seq_tile(const tile_geom g
 // the LDS reservation, then the weight permutation, the snapshot, the zero fill, then the kernel: an error return never follows
 // a launch of the layer kernel
 template <int MT, bool R, bool WLDS>
-static int launch_tile(const tile_geom &g, size_t lds_bytes, bool shared_words, const uint32_t *spk_in, const float *W, float *scratch,
-                       const float *b, const float *tau4, float *eps0, float *eps1, float *arp, uint32_t *spk_out, float *pv_out,
-                       float *v_out, int T, int B, float alpharp, float wrp, hipStream_t st, const char *name)
+static int launch_tile(const dcll_conv_desc *d, const tile_geom &g, size_t lds_bytes, bool shared_words, const uint32_t *spk_in,
+                       const float *W, float *scratch, const float *b, const float *tau4, float *eps0, float *eps1, float *arp,
+                       uint32_t *spk_out, float *pv_out, float *v_out, int T, int B, float alpharp, float wrp, hipStream_t st, const char *name)
 {
     if (hipFuncSetAttribute((const void *)k_lif_seq_tile<MT, R, WLDS>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)lds_bytes) != hipSuccess) {
         (void)hipGetLastError();
         return fail(DCLL_ERR_LAUNCH, "k_lif_seq_tile: cannot reserve its LDS");
     }
-    const int n = g.nsteps * 64 * MT;
-    const size_t nin = (size_t)B * g.c_in * g.h * g.w;
-    float *snap0 = scratch + n, *snap1 = snap0 + nin;
-    hipLaunchKernelGGL(k_seq_tile_wprep, dim3((n + 255) / 256), dim3(256), 0, st, W, scratch, g.c_in, g.c_out, g.kh, g.kw, g.npair,
-                       g.nsteps, MT);
-    hipError_t e = hipGetLastError();           // (not in the launch log, like k_seq_band_wprep)
-    if (e == hipSuccess) e = hipMemcpyAsync(snap0, eps0, nin * sizeof(float), hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(snap1, eps1, nin * sizeof(float), hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess && shared_words && spk_out)
-        e = hipMemsetAsync(spk_out, 0, (size_t)T * B * g.c_out * g.ow * sizeof(uint32_t), st);
-    if (e != hipSuccess) {
-        snprintf(dcll_err_buf(), DCLL_ERR_LEN, "k_lif_seq_tile (weight permutation, state snapshot, zero fill): %s", hipGetErrorString(e));
-        return DCLL_ERR_LAUNCH;
-    }
+    float *snap0, *snap1;
+    const int rc = seq_split_prepare(d, W, scratch, MT, eps0, eps1, spk_out, (size_t)T * B * g.c_out * g.ow, shared_words, B, st,
+                                     "k_lif_seq_tile", &snap0, &snap1);
+    if (rc) return rc;
     hipLaunchKernelGGL((k_lif_seq_tile<MT, R, WLDS>), dim3((unsigned)((long)B * g.NY * g.NX)), dim3(TILE_THREADS), lds_bytes, st, g,
                        spk_in, scratch, b, tau4, snap0, snap1, eps0, eps1, arp, spk_out, pv_out, v_out, T, B, alpharp, wrp);
     HIP_CHECK_LAUNCH(name);
@@ -604,8 +430,8 @@ extern "C" int dcll_conv_lif_sequence_tiles(const dcll_conv_desc *d, const uint3
     conv_shape(d, &g.ch, &g.cw, &g.ph, &g.pw);
     g.CP = g.ch * g.cw;
     g.PP = g.ph * g.pw;
-    g.npair = (d->c_in / 2) * d->kh * d->kw;
-    g.nsteps = (int)tile_steps(d);
+    g.npair = (int)any_chain_pairs(d);
+    g.nsteps = (int)any_chain_steps(d);
     g.iw = (d->h * d->w + 31) / 32;
     g.ow = (g.PP + 31) / 32;
     g.NY = NY;
@@ -624,36 +450,17 @@ extern "C" int dcll_conv_lif_sequence_tiles(const dcll_conv_desc *d, const uint3
             for (int py = ry.P0; py < ry.P1 && !shared_words; ++py) shared_words = ((long)py * g.pw + rx.P0) % 32 != 0;
         }
     }
-    if (base * 4 > TILE_LDS_MAX || base * 4 != dcll_conv_lif_sequence_tiles_lds(d, NY, NX))
+    if (base * 4 > ANY_LDS_MAX || base * 4 != dcll_conv_lif_sequence_tiles_lds(d, NY, NX))
         return fail(DCLL_ERR_LAUNCH, "a tile's LDS beyond the limit", who);
     g.o_w = (int)base;
-    // weights that do not fit as a whole: a grid of more than one workgroup per CU keeps half of the LDS free so that two tiles
-    // share a CU (the rule of k_lif_seq_band)
-    const long per = 64 * MT;
-    const bool whole = (base + (long)g.nsteps * per) * 4 <= TILE_LDS_MAX;
-    const long budget = (!whole && (long)B * NT > TILE_CUS && base * 4 * 2 <= TILE_LDS_MAX) ? TILE_LDS_MAX / 2 : TILE_LDS_MAX;
-    const long room = (budget / 4 - base) / per;
-    g.nwl = (int)(room < g.nsteps ? room : g.nsteps);
+    g.nwl = seq_weight_room(base, g.nsteps, MT, (long)B * NT);
     const bool wlds = g.nwl == g.nsteps;
-    const size_t lds_bytes = (size_t)(base + (long)g.nwl * per) * 4;
+    const size_t lds_bytes = (size_t)(base + (long)g.nwl * 64 * MT) * 4;
 
     // launch-log names: k_lif_seq_tile<M tiles, refractory, weights in LDS>
 #define DCLL_TILE(M_, R_, L_)                                                                                                   \
-    return launch_tile<M_, R_, L_>(g, lds_bytes, shared_words, spk_in, W, scratch, b, tau4, eps0, eps1, arp, spk_out, pv_out,   \
+    return launch_tile<M_, R_, L_>(d, g, lds_bytes, shared_words, spk_in, W, scratch, b, tau4, eps0, eps1, arp, spk_out, pv_out,  \
                                    v_out, T, B, d->alpharp, d->wrp, st, "k_lif_seq_tile<" #M_ "," #R_ "," #L_ ">")
-    if (MT == 1) {
-        if (d->refractory) {
-            if (wlds) DCLL_TILE(1, 1, 1);
-            DCLL_TILE(1, 1, 0);
-        }
-        if (wlds) DCLL_TILE(1, 0, 1);
-        DCLL_TILE(1, 0, 0);
-    }
-    if (d->refractory) {
-        if (wlds) DCLL_TILE(2, 1, 1);
-        DCLL_TILE(2, 1, 0);
-    }
-    if (wlds) DCLL_TILE(2, 0, 1);
-    DCLL_TILE(2, 0, 0);
+    DCLL_SEQ_SPLIT_DISPATCH(DCLL_TILE, MT, d->refractory, wlds);
 #undef DCLL_TILE
 }

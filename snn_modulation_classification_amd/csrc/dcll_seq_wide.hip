@@ -24,17 +24,16 @@
 // an odd c_in pairs its taps; a chain of odd length ends with a zero link.  M = c_out padded to 64 rows (zero weights), N = 32
 // pixels of the flattened conv plane; a wave owns whole pixel tiles and runs BOTH 32-row chains of a tile itself, interleaved:
 // one LDS read of the B operand feeds two MFMAs, one per M tile.  The two chains are independent and each is unsplit, so every
-// v is still ONE fmaf chain.  Weights are permuted in front of every launch (k_seq_wide_wprep, nothing cached):
+// v is still ONE fmaf chain.  Weights are permuted in front of every launch (k_seq_any_wprep at MT = 2, nothing cached):
 // wperm[m][mt][lane] = weight of link 2 m + (lane >> 5) for output channel 32 mt + (lane & 31) — one coalesced 512-byte read per
 // step and wave.
 //
 // One step = the three phases of k_lif_seq_any (A traces + pooling pass of the previous step, B chains -> vpl, C refractory
 // update + v_out), a barrier behind each.  State is read once before the first step and written once behind the last.
-#include "dcll_internal.h"
+#include "dcll_any_shared.h"
 
 constexpr int WIDE_THREADS = 512, WIDE_NW = WIDE_THREADS / 64;
-constexpr long WIDE_LDS_MAX = 160 * 1024;
-constexpr int WIDE_MAX_K = 16, WIDE_MAX_COUT = 64, WIDE_MT = 2;
+constexpr int WIDE_MAX_COUT = 64, WIDE_MT = 2;
 constexpr int WIDE_KE = 36;         // register form: eps0 values per thread (one pixel tile per wave)
 
 struct wide_geom {
@@ -58,11 +57,6 @@ static inline long wide_lds_floats(const dcll_conv_desc *d)
     const long vpl = (long)d->c_out * ch * cw;
     return img + e0 + vpl * (d->refractory ? 2 : 1) + 4L * d->c_in + 32 * WIDE_MT;
 }
-static inline long wide_steps(const dcll_conv_desc *d)
-{
-    const long KK = (long)d->kh * d->kw;
-    return (d->c_in / 2) * KK + ((d->c_in & 1) ? (KK + 1) / 2 : 0);
-}
 
 // the register form's set: img + tau + bias; for layers without pooling within its per-thread / per-wave register arrays
 static inline long wide_lds_floats_regs(const dcll_conv_desc *d)
@@ -74,20 +68,17 @@ static inline bool wide_regs_ok(const dcll_conv_desc *d)
     int ch, cw, ph, pw;
     conv_shape(d, &ch, &cw, &ph, &pw);
     return d->pool_h == 1 && d->pool_w == 1 && (long)d->c_in * d->h * d->w <= (long)WIDE_KE * WIDE_THREADS &&
-           (long)ch * cw <= 32L * WIDE_NW && wide_lds_floats_regs(d) * 4 <= WIDE_LDS_MAX;
+           (long)ch * cw <= 32L * WIDE_NW && wide_lds_floats_regs(d) * 4 <= ANY_LDS_MAX;
 }
 
 // the support predicate of the layers this file serves or forwards: DCLL_OK (*regs: the register form serves the layer; c_out <=
 // 32: the answer is dcll_conv_lif_sequence_any's), or the refusal with its message
 static int wide_supported(const dcll_conv_desc *d, const char *who, bool *regs = nullptr)
 {
-    int rc = check_desc(d);
+    int rc = any_layer_ok(d, WIDE_MAX_COUT, who);
     if (rc) return rc;
-    if (!plain_conv(d)) return fail(DCLL_ERR_UNSUPPORTED, "plain convolutions only: stride, dilation and groups must be 1", who);
-    if (d->c_out > WIDE_MAX_COUT) return fail(DCLL_ERR_UNSUPPORTED, "c_out <= 64 (two 32-row MFMA tiles of output channels)", who);
-    if (d->kh > WIDE_MAX_K || d->kw > WIDE_MAX_K) return fail(DCLL_ERR_UNSUPPORTED, "kernels up to 16x16", who);
     if (d->c_out <= 32) return dcll_conv_lif_sequence_any_lds(d) > 0 ? DCLL_OK : DCLL_ERR_UNSUPPORTED;     // (its message stands)
-    const bool full = wide_lds_floats(d) * 4 <= WIDE_LDS_MAX;
+    const bool full = wide_lds_floats(d) * 4 <= ANY_LDS_MAX;
     if (!full && !wide_regs_ok(d))
         return fail(DCLL_ERR_UNSUPPORTED, "the per-sample working set (padded eps1 image, eps0, the v plane) exceeds the 160 KiB of LDS "
                                           "and the layer is outside the register form (no pooling, c_in h w <= 18432, ch cw <= 256)", who);
@@ -106,26 +97,7 @@ extern "C" int64_t dcll_conv_lif_sequence_wide_scratch(const dcll_conv_desc *d)
 {
     if (wide_supported(d, "dcll_conv_lif_sequence_wide_scratch") != DCLL_OK) return 0;
     if (d->c_out <= 32) return dcll_conv_lif_sequence_any_scratch(d);
-    return wide_steps(d) * 64 * WIDE_MT;
-}
-
-// W (c_out, c_in, kh, kw) -> wperm[m][mt][lane]: link 2 m + h of channel co = 32 mt + (lane & 31), h = lane >> 5; 0 beyond
-// c_out / the chain
-__global__ void k_seq_wide_wprep(const float *__restrict__ W, float *__restrict__ wperm, int c_in, int c_out, int kh, int kw,
-                                 int npair, int nsteps)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nsteps * 64 * WIDE_MT) return;
-    const int m = i >> 7, mt = (i >> 6) & 1, lane = i & 63, co = 32 * mt + (lane & 31), h = lane >> 5, KK = kh * kw;
-    int ci, tap;
-    if (m < npair) {
-        ci = 2 * (m / KK) + h;
-        tap = m % KK;
-    } else {
-        ci = c_in - 1;
-        tap = 2 * (m - npair) + h;
-    }
-    wperm[i] = (co < c_out && tap < KK) ? W[((long)co * c_in + ci) * KK + tap] : 0.0f;
+    return any_chain_steps(d) * 64 * WIDE_MT;
 }
 
 struct f32x16x2 {
@@ -411,8 +383,8 @@ __global__ __launch_bounds__(WIDE_THREADS) void k_lif_seq_wide(const wide_geom g
 
 // the LDS reservation, then the weight permutation, then the kernel: an error return never follows a launch
 template <bool R, bool WLDS, bool REGS>
-static int launch_wide(const wide_geom &g, size_t lds_bytes, const uint32_t *spk_in, const float *W, float *wperm, const float *b,
-                       const float *tau4, float *eps0, float *eps1, float *arp, uint32_t *spk_out, float *pv_out, float *v_out,
+static int launch_wide(const dcll_conv_desc *d, const wide_geom &g, size_t lds_bytes, const uint32_t *spk_in, const float *W,
+                       float *wperm, const float *b, const float *tau4, float *eps0, float *eps1, float *arp, uint32_t *spk_out, float *pv_out, float *v_out,
                        int T, int B, float alpharp, float wrp, hipStream_t st, const char *name)
 {
     if (hipFuncSetAttribute((const void *)k_lif_seq_wide<R, WLDS, REGS>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -420,16 +392,8 @@ static int launch_wide(const wide_geom &g, size_t lds_bytes, const uint32_t *spk
         (void)hipGetLastError();
         return fail(DCLL_ERR_LAUNCH, "k_lif_seq_wide: cannot reserve its LDS");
     }
-    const int n = g.nsteps * 64 * WIDE_MT;
-    hipLaunchKernelGGL(k_seq_wide_wprep, dim3((n + 255) / 256), dim3(256), 0, st, W, wperm, g.c_in, g.c_out, g.kh, g.kw, g.npair,
-                       g.nsteps);
-    {
-        hipError_t e = hipGetLastError();       // (not in the launch log, like k_seq_any_wprep)
-        if (e != hipSuccess) {
-            snprintf(dcll_err_buf(), DCLL_ERR_LEN, "k_seq_wide_wprep: %s", hipGetErrorString(e));
-            return DCLL_ERR_LAUNCH;
-        }
-    }
+    const int rc = dcll_launch_seq_wprep(d, W, wperm, WIDE_MT, st, false);       // (not in the launch log)
+    if (rc) return rc;
     hipLaunchKernelGGL((k_lif_seq_wide<R, WLDS, REGS>), dim3(B), dim3(WIDE_THREADS), lds_bytes, st, g, spk_in, wperm, b, tau4, eps0,
                        eps1, arp, spk_out, pv_out, v_out, T, B, alpharp, wrp);
     HIP_CHECK_LAUNCH(name);
@@ -460,8 +424,8 @@ extern "C" int dcll_conv_lif_sequence_wide(const dcll_conv_desc *d, const uint32
     conv_shape(d, &g.ch, &g.cw, &g.ph, &g.pw);
     g.CP = g.ch * g.cw;
     g.PP = g.ph * g.pw;
-    g.npair = (d->c_in / 2) * d->kh * d->kw;
-    g.nsteps = (int)wide_steps(d);
+    g.npair = (int)any_chain_pairs(d);
+    g.nsteps = (int)any_chain_steps(d);
     g.iw = (d->h * d->w + 31) / 32;
     g.ow = (g.PP + 31) / 32;
     g.o_e0 = d->c_in * g.CHS;
@@ -474,20 +438,14 @@ extern "C" int dcll_conv_lif_sequence_wide(const dcll_conv_desc *d, const uint32
     const long base = g.o_w;
     if (base != (regs ? wide_lds_floats_regs(d) : wide_lds_floats(d)))      // the layout above against the ONE exported formula
         return fail(DCLL_ERR_LAUNCH, "LDS layout and dcll_conv_lif_sequence_wide_lds disagree", who);
-    // weights that do not fit as a whole: a grid of more than one workgroup per CU (256 CUs) keeps half of the LDS free so that
-    // two samples share a CU (the rule of k_lif_seq_any)
-    const long per = 64 * WIDE_MT;
-    const bool whole = (base + (long)g.nsteps * per) * 4 <= WIDE_LDS_MAX;
-    const long budget = (!whole && B > 256 && base * 4 * 2 <= WIDE_LDS_MAX) ? WIDE_LDS_MAX / 2 : WIDE_LDS_MAX;
-    const long room = (budget / 4 - base) / per;
-    g.nwl = (int)(room < g.nsteps ? room : g.nsteps);
+    g.nwl = seq_weight_room(base, g.nsteps, WIDE_MT, B);
     const bool wlds = !regs && g.nwl == g.nsteps;
-    const size_t lds_bytes = (size_t)(base + (long)g.nwl * per) * 4;
+    const size_t lds_bytes = (size_t)(base + (long)g.nwl * 64 * WIDE_MT) * 4;
 
     // launch-log names: k_lif_seq_wide<refractory, weights in LDS, register form>
 #define DCLL_WIDE(R_, L_, G_)                                                                                                 \
-    return launch_wide<R_, L_, G_>(g, lds_bytes, spk_in, W, w_scratch, b, tau4, eps0, eps1, arp, spk_out, pv_out, v_out, T, B, \
-                                   d->alpharp, d->wrp, st, "k_lif_seq_wide<" #R_ "," #L_ "," #G_ ">")
+    return launch_wide<R_, L_, G_>(d, g, lds_bytes, spk_in, W, w_scratch, b, tau4, eps0, eps1, arp, spk_out, pv_out, v_out, T,    \
+                                   B, d->alpharp, d->wrp, st, "k_lif_seq_wide<" #R_ "," #L_ "," #G_ ">")
     if (d->refractory) {
         if (regs) DCLL_WIDE(1, 0, 1);
         if (wlds) DCLL_WIDE(1, 1, 0);

@@ -26,7 +26,7 @@
 // advanced in the kernel — a workgroup would read halo rows of eps1 that a sibling of the same sample is overwriting in
 // place (the read-after-write race once found in k_lif_seq_w3f) — the launcher runs k_trace first and the kernel stages the
 // rows of eps1 its tiles touch read-only.  Every chain is still whole, so the results do not depend on NS.
-#include "dcll_internal.h"
+#include "dcll_any_shared.h"
 #include <mutex>
 
 constexpr int SA_THREADS = 512, SA_NW = SA_THREADS / 64;
@@ -80,7 +80,7 @@ extern "C" int64_t dcll_conv_lif_step_any_lds(const dcll_conv_desc *d)
 // floats of w_scratch: 64 per MFMA step of a chain (k_seq_any_wprep's fragment order); 0 = not served
 extern "C" int64_t dcll_conv_lif_step_any_scratch(const dcll_conv_desc *d)
 {
-    return dcll_step_any_check(d, "dcll_conv_lif_step_any_scratch") == DCLL_OK ? dcll_seq_any_steps(d) * 64 : 0;
+    return dcll_step_any_check(d, "dcll_conv_lif_step_any_scratch") == DCLL_OK ? any_chain_steps(d) * 64 : 0;
 }
 
 // workgroups per sample, a pure function of (descriptor, B): 1 = the fused form.  min(ceil(tiles / waves), 256 / B), then the
@@ -306,8 +306,8 @@ int dcll_launch_step_any(const dcll_conv_desc *d, const float *x, const float *w
     conv_shape(d, &g.ch, &g.cw, &g.ph, &g.pw);
     g.CP = g.ch * g.cw;
     g.PP = g.ph * g.pw;
-    g.npair = (d->c_in / 2) * d->kh * d->kw;
-    g.nsteps = (int)dcll_seq_any_steps(d);
+    g.npair = (int)any_chain_pairs(d);
+    g.nsteps = (int)any_chain_steps(d);
     const int ntl = (g.CP + 31) / 32;
     g.ns = ns;
     g.tpb = (ntl + ns - 1) / ns;

@@ -29,14 +29,12 @@
 // tiles costs only the second B read.  The traces are NOT advanced in the kernel (the read-after-write race of k_lif_step_any's
 // note): the entry point runs k_trace first and a workgroup stages, read-only, the padded rows its units' tiles touch.  Two
 // workgroups may hold the two M tiles of one pixel tile: both stage that tile's rows; their outputs and arp elements are disjoint.
-#include "dcll_internal.h"
+#include "dcll_any_shared.h"
 #include <mutex>
 
 constexpr int SW_THREADS = 512, SW_NW = SW_THREADS / 64;
-constexpr long SW_LDS_MAX = 160 * 1024;
-constexpr int SW_MAX_K = 16, SW_MAX_COUT = 64, SW_MT = 2;
+constexpr int SW_MAX_COUT = 64, SW_MT = 2;
 constexpr int SW_MAX_DEVICES = 64;
-constexpr int SW_CUS = 256;                     // the chip's CUs (the constant of the other launchers' batch rules)
 // split rule: units a workgroup should keep (one chain per SIMD when CUs are idle); -D for experiments/build_variant.sh
 #ifndef DCLL_STEP_WIDE_UNITS
 #define DCLL_STEP_WIDE_UNITS 4
@@ -68,11 +66,6 @@ static inline long step_wide_lds_floats(const dcll_conv_desc *d)
     const long vpl = step_wide_pooled(d) ? (long)d->c_out * ch * cw : 0;
     return img + vpl + 32 * SW_MT;
 }
-static inline long step_wide_steps(const dcll_conv_desc *d)
-{
-    const long KK = (long)d->kh * d->kw;
-    return (d->c_in / 2) * KK + ((d->c_in & 1) ? (KK + 1) / 2 : 0);
-}
 
 // the support predicate of the layers this file serves or forwards: DCLL_OK (c_out <= 32: the answer and the message are
 // dcll_conv_lif_step_any's), or the refusal with its message
@@ -83,8 +76,8 @@ int dcll_step_wide_check(const dcll_conv_desc *d, const char *who)
     if (!plain_conv(d)) return fail(DCLL_ERR_UNSUPPORTED, "plain convolutions only: stride, dilation and groups must be 1", who);
     if (d->c_out > SW_MAX_COUT) return fail(DCLL_ERR_UNSUPPORTED, "c_out <= 64 (two 32-row MFMA tiles of output channels)", who);
     if (d->c_out <= 32) return dcll_step_any_check(d, "dcll_conv_lif_step_any");
-    if (d->kh > SW_MAX_K || d->kw > SW_MAX_K) return fail(DCLL_ERR_UNSUPPORTED, "kernels up to 16x16", who);
-    if (step_wide_lds_floats(d) * 4 > SW_LDS_MAX)
+    if (d->kh > ANY_MAX_K || d->kw > ANY_MAX_K) return fail(DCLL_ERR_UNSUPPORTED, "kernels up to 16x16", who);
+    if (step_wide_lds_floats(d) * 4 > ANY_LDS_MAX)
         return fail(DCLL_ERR_UNSUPPORTED, "the per-sample working set (padded eps1 image, the v plane of a pooling layer) exceeds "
                                           "the 160 KiB of LDS", who);
     return DCLL_OK;
@@ -100,7 +93,7 @@ extern "C" int64_t dcll_conv_lif_step_wide_lds(const dcll_conv_desc *d)
 extern "C" int64_t dcll_conv_lif_step_wide_scratch(const dcll_conv_desc *d)
 {
     if (dcll_step_wide_check(d, "dcll_conv_lif_step_wide_scratch") != DCLL_OK) return 0;
-    return d->c_out <= 32 ? dcll_conv_lif_step_any_scratch(d) : step_wide_steps(d) * 64 * SW_MT;
+    return d->c_out <= 32 ? dcll_conv_lif_step_any_scratch(d) : any_chain_steps(d) * 64 * SW_MT;
 }
 
 // workgroups per sample, a pure function of (descriptor, B): 1 = the fused form.  units = 2 tiles; ns0 = min(ceil(units / 4),
@@ -112,7 +105,7 @@ int dcll_step_wide_split(const dcll_conv_desc *d, int32_t B)
     conv_shape(d, &ch, &cw, &ph, &pw);
     const int units = SW_MT * ((ch * cw + 31) / 32);
     int ns = (units + SW_UNITS - 1) / SW_UNITS;
-    if (ns > SW_CUS / B) ns = SW_CUS / B;
+    if (ns > ANY_CUS / B) ns = ANY_CUS / B;
     if (ns <= 1) return 1;
     const int upw = (units + ns - 1) / ns;
     return (units + upw - 1) / upw;
@@ -127,19 +120,13 @@ __global__ void k_step_wide_wprep(const float *__restrict__ W, float *__restrict
     if (i >= nsteps * 64 * SW_MT) return;
     const int m = i >> 7, lane = (i >> 1) & 63, mt = i & 1, co = 32 * mt + (lane & 31), h = lane >> 5, KK = kh * kw;
     int ci, tap;
-    if (m < npair) {
-        ci = 2 * (m / KK) + h;
-        tap = m % KK;
-    } else {
-        ci = c_in - 1;
-        tap = 2 * (m - npair) + h;
-    }
+    any_link(m, h, npair, c_in, KK, ci, tap);
     wperm[i] = (co < c_out && tap < KK) ? W[((long)co * c_in + ci) * KK + tap] : 0.0f;
 }
 
 int dcll_launch_step_wide_wprep(const dcll_conv_desc *d, const float *W, float *wperm, hipStream_t st)
 {
-    const int npair = (d->c_in / 2) * d->kh * d->kw, nsteps = (int)step_wide_steps(d);
+    const int npair = (int)any_chain_pairs(d), nsteps = (int)any_chain_steps(d);
     hipLaunchKernelGGL(k_step_wide_wprep, dim3((nsteps * 64 * SW_MT + 255) / 256), dim3(256), 0, st, W, wperm, d->c_in, d->c_out,
                        d->kh, d->kw, npair, nsteps);
     HIP_CHECK_LAUNCH("k_step_wide_wprep");
@@ -419,8 +406,8 @@ int dcll_launch_step_wide(const dcll_conv_desc *d, const float *x, const float *
     conv_shape(d, &g.ch, &g.cw, &g.ph, &g.pw);
     g.CP = g.ch * g.cw;
     g.PP = g.ph * g.pw;
-    g.npair = (d->c_in / 2) * d->kh * d->kw;
-    g.nsteps = (int)step_wide_steps(d);
+    g.npair = (int)any_chain_pairs(d);
+    g.nsteps = (int)any_chain_steps(d);
     const int units = SW_MT * ((g.CP + 31) / 32);
     g.ns = ns;
     g.upw = ns >= 1 ? (units + ns - 1) / ns : units;
