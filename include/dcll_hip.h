@@ -643,6 +643,42 @@ int dcll_conv_lif_sequence_tiles(const dcll_conv_desc *d, const uint32_t *spk_in
                                  void *stream);
 
 /*
+ * Still ABI 10 (four more symbols, found by lookup) — dcll_conv_lif_sequence_tiles for layers of MORE than 64 output channels
+ * (k_lif_seq_slab, csrc/dcll_seq_slab.hip): the tile kernel with one more grid dimension, B x tiles_y x tiles_x x NS.  The slab rule:
+ * NS = ceil(c_out / 64) <= 65 535; slab s owns the output channels [64 s, min(64 s + 64, c_out)); rows at or beyond c_out are never
+ * stored.  Arguments, buffer formats and arithmetic are dcll_conv_lif_sequence_tiles'; every v is ONE unsplit chain in the pinned
+ * order, so v, pv, spikes and the final state are bit-identical to dcll_conv_lif_sequence_tiles run on each 64-channel slice of the
+ * layer (W, b, arp) with the same plan.  Additions only: the calls above, their refusals ("c_out <= 64") and kernels are unchanged.
+ *   c_out <= 64   every one of the four calls IS its _tiles twin (kernels, launch-log names, bits, refusals, _lds / _scratch values).
+ *   workgroup     (sample, tile, slab): holds the traces of ALL c_in channels of its tile, as a tile workgroup does, and vpl, arp,
+ *                 bias and the weights kept in LDS for its slab only.  Every slab recomputes the tile's traces; slab 0 alone writes
+ *                 eps0 / eps1 back; every slab writes its own arp, pv, v and spike planes (a spike word belongs to one channel; inside
+ *                 a channel the tile call's store-or-OR rule stands).  A last slab of at most 32 channels runs one chain per pixel tile.
+ *   tiles         (0, 0): the fitting (NY, NX) with the fewest tiles, from ONE tile up, ties to the smallest sum of held input elements,
+ *                 then to the smaller NX — derived from the LDS formula alone, no measurement stands behind it.  Otherwise exactly
+ *                 (tiles_y, tiles_x), 1 x 1 and N x 1 included: this kernel runs every plan itself.  A 0 in one place only:
+ *                 DCLL_ERR_INVALID.  The plan of a tile is dcll_conv_lif_sequence_tiles'.
+ *   LDS           dcll_conv_lif_sequence_tiles' formula with the slab's channel count, 64, in place of c_out (MT = 2): it does not
+ *                 grow with c_out.  Behind it as many permuted weight steps (128 floats each) as fit, by the same rule with
+ *                 B NY NX NS workgroups.
+ *   scratch       dcll_conv_lif_sequence_slabs_scratch(d, B) floats = 64 ceil(c_out / 32) per MFMA step of a chain (the ONE weight
+ *                 permutation of the whole layer; a slab reads its two columns) + 2 B c_in h w (the snapshot of eps0 / eps1).
+ * _plan, _lds, _scratch: as the _tiles calls (host-only).  DCLL_ERR_UNSUPPORTED, before any launch: stride / dilation / groups other
+ * than 1, a kernel beyond 16x16, more than 65 535 slabs, tiles_y > ph or tiles_x > pw, an explicit plan whose largest set does not
+ * fit, no plan that fits.  DCLL_ERR_INVALID, before any launch: a negative count, a 0 in one place only, a NULL required pointer, a
+ * refractory layer without arp, T < 0 or B < 0, B NY NX beyond the grid.  T == 0 or B == 0: DCLL_OK.  Launch log:
+ * k_lif_seq_slab<R,WLDS> (refractory, all weights in LDS); the weight permutation, the snapshot and the zero fill stay out of it.
+ */
+int32_t dcll_conv_lif_sequence_slabs_plan(const dcll_conv_desc *d, int32_t B, int32_t tiles_y, int32_t tiles_x, int32_t *ny_nx,
+                                          int32_t *bounds_y, int32_t *bounds_x);
+int64_t dcll_conv_lif_sequence_slabs_lds(const dcll_conv_desc *d, int32_t tiles_y, int32_t tiles_x);
+int64_t dcll_conv_lif_sequence_slabs_scratch(const dcll_conv_desc *d, int32_t B);
+int dcll_conv_lif_sequence_slabs(const dcll_conv_desc *d, const uint32_t *spk_in, const float *W, const float *b,
+                                 const float *tau4, float *eps0, float *eps1, float *arp, uint32_t *spk_out, float *pv_out,
+                                 float *v_out, float *scratch, int32_t T, int32_t B, int32_t tiles_y, int32_t tiles_x,
+                                 void *stream);
+
+/*
  * ABI 9 — the backward of one layer step with the weight gradient of ANY plain conv layer on fp32-MFMA tiles (k_bwd_wgrad_any):
  * dcll_conv_lif_backward / dcll_conv_lif_backward_open with the same arguments, results and scratch rule (B c_out ch cw +
  * k (c_out (c_in kh kw + 1)) floats, k >= 1; less: DCLL_ERR_INVALID), for the layers whose weight gradient the calls above
@@ -703,6 +739,42 @@ int dcll_conv_lif_backward_wide(const dcll_conv_desc *d, const float *eps1, cons
                                 float *dW, float *db, float *d_outW, float *d_outb, float *scratch, int64_t scratch_floats,
                                 int32_t B, void *stream);
 int dcll_conv_lif_backward_wide_open(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                                     const float *g_p, const float *g_o, const float *g_pv, const float *g_v, const float *i2o_W,
+                                     float *d_outW, float *d_outb, float *scratch, int64_t scratch_floats, int32_t B,
+                                     const float **part, int32_t *nchunk, void *stream);
+
+/*
+ * Added under ABI 10 (DCLL_ABI_VERSION is unchanged: a caller detects these three symbols by symbol lookup) — the calls above for
+ * the layers of MORE than 64 output channels that a --netscale above 2 makes (k_bwd_wgrad_slab, csrc/dcll_bwd_slab.hip): arguments,
+ * results and scratch rule of dcll_conv_lif_backward_wide / _wide_open (scratch_floats >= B c_out ch cw + k (c_out (c_in kh kw + 1)),
+ * k >= 1 partial rows, at most 256 are used; less: DCLL_ERR_INVALID).  Additions only: the default dispatch, the _any and _wide
+ * calls, their launch logs and refusals (dcll_conv_lif_backward_wide's "c_out <= 64" included) are unchanged; dv, the fixed-order
+ * reduction and the output_ gradient are the same kernels (they take rows of any c_out).
+ * The slab rule: NS = ceil(c_out / 64); slab s owns the output channels [64 s, min(64 s + 64, c_out)), two 32-row M tiles;
+ * rows at or beyond c_out are never stored; NS <= 65 535 (the grid's third dimension, the only new bound).
+ * Served (else DCLL_ERR_UNSUPPORTED, before any launch): stride = dilation = groups = 1; any c_in; any c_out up to 64 x 65 535;
+ * kh, kw <= 16; any padding, pooling and batch; and a smallest working set within the 160 KiB of LDS of a workgroup, which does
+ * NOT grow with c_out: 4 bytes x (cg (h + 2 pad_h)(w + 2 pad_w) + 1 + min(c_out, 64) (ch (cw rounded up to even) | 1)).
+ * c_out <= 64: the call IS dcll_conv_lif_backward_wide[_open] (c_out <= 32: _any[_open]) — same kernels, launch log, bits,
+ * refusals (with that call's name in the message) and _lds value — so a network of mixed widths goes through one entry point.
+ * c_out > 64: k_bwd_wgrad_wide's decomposition with blockIdx.z as the slab.  A workgroup stages only its slab's rows of the dv
+ * plane and stores part[chunk][co][...] with the global co; the bias gradient of a slab comes from the workgroup with the first
+ * column tiles of that slab.  Column split, pixel split (pieces added in wave order), the 256-chunk limit and the odd-cw rule are
+ * unchanged; the small-batch lowering aims chunks x column splits x slabs at the CU count (never more LDS than the full launch).
+ * The launch plan is a function of (descriptor, B) alone.  The launch log names the form, NQ = column tiles per wave (1, 2, 4):
+ * "k_bwd_wgrad_slab<NQ>", "k_bwd_wgrad_slab<NQ> (column split)", "k_bwd_wgrad_slab<1> (pixel split)" or
+ * "k_bwd_wgrad_slab<1> (column split, pixel split)".
+ * Every sum has a fixed order: two runs give the same bits, and _slab_open + dcll_grad_reduce_adam gives _slab's bits.  A row of
+ * dW is summed as k_bwd_wgrad_wide sums it under the same (TPW, PS, chunks).  Not bit-identical to dcll_conv_lif_backward.
+ * dcll_conv_lif_backward_slab_lds returns the LDS bytes per workgroup of a full launch (no launch uses more; c_out <= 64:
+ * dcll_conv_lif_backward_wide_lds), or 0 for a descriptor that is not served (invalid ones included).
+ */
+int64_t dcll_conv_lif_backward_slab_lds(const dcll_conv_desc *d);
+int dcll_conv_lif_backward_slab(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                                const float *g_p, const float *g_o, const float *g_pv, const float *g_v, const float *i2o_W,
+                                float *dW, float *db, float *d_outW, float *d_outb, float *scratch, int64_t scratch_floats,
+                                int32_t B, void *stream);
+int dcll_conv_lif_backward_slab_open(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
                                      const float *g_p, const float *g_o, const float *g_pv, const float *g_v, const float *i2o_W,
                                      float *d_outW, float *d_outb, float *scratch, int64_t scratch_floats, int32_t B,
                                      const float **part, int32_t *nchunk, void *stream);

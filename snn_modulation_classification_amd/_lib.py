@@ -155,6 +155,10 @@ SIGNATURES = {
     "dcll_conv_lif_sequence_tiles_lds": (_I64, [_DP, _I32, _I32]),
     "dcll_conv_lif_sequence_tiles_scratch": (_I64, [_DP, _I32]),
     "dcll_conv_lif_sequence_tiles": (_I32, [_DP] + [_P] * 11 + [_I32, _I32, _I32, _I32, _P]),
+    "dcll_conv_lif_sequence_slabs_plan": (_I32, [_DP, _I32, _I32, _I32, _IP, _IP, _IP]),
+    "dcll_conv_lif_sequence_slabs_lds": (_I64, [_DP, _I32, _I32]),
+    "dcll_conv_lif_sequence_slabs_scratch": (_I64, [_DP, _I32]),
+    "dcll_conv_lif_sequence_slabs": (_I32, [_DP] + [_P] * 11 + [_I32, _I32, _I32, _I32, _P]),
     "dcll_pack_spike_planes": (_I32, [_P, _P, _I64, _I32, _P]),
     "dcll_unpack_spike_planes": (_I32, [_P, _P, _I64, _I32, _P]),
     "dcll_conv_lif_backward_any_lds": (_I64, [_DP]),
@@ -163,6 +167,9 @@ SIGNATURES = {
     "dcll_conv_lif_backward_wide_lds": (_I64, [_DP]),
     "dcll_conv_lif_backward_wide": (_I32, [_DP] + [_P] * 13 + [_I64, _I32, _P]),
     "dcll_conv_lif_backward_wide_open": (_I32, [_DP] + [_P] * 11 + [_I64, _I32, ctypes.POINTER(ctypes.c_void_p), _IP, _P]),
+    "dcll_conv_lif_backward_slab_lds": (_I64, [_DP]),
+    "dcll_conv_lif_backward_slab": (_I32, [_DP] + [_P] * 13 + [_I64, _I32, _P]),
+    "dcll_conv_lif_backward_slab_open": (_I32, [_DP] + [_P] * 11 + [_I64, _I32, ctypes.POINTER(ctypes.c_void_p), _IP, _P]),
     "dcll_conv_lif_step_any_lds": (_I64, [_DP]),
     "dcll_conv_lif_step_any_scratch": (_I64, [_DP]),
     "dcll_conv_lif_step_any": (_I32, [_DP] + [_P] * 20 + [_I32, _P]),

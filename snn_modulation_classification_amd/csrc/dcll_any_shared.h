@@ -31,6 +31,21 @@ static inline int any_layer_ok(const dcll_conv_desc *d, int max_cout, const char
     return DCLL_OK;
 }
 
+// The slab rule of the kernels that go past 64 output channels (k_bwd_wgrad_slab; tests/bwd_slab_cases.py restates it): output
+// channels are independent of one another, so a layer of c_out > 64 channels is cut into NS = ceil(c_out / 64) slabs of two 32-row
+// M tiles, one more grid dimension.  Slab s owns the channels [64 s, min(64 s + 64, c_out)); rows at or beyond c_out are never
+// stored; a last slab of at most 32 channels has an empty second M tile.  The only new bound is the grid's: NS <= 65 535.
+// A layer of c_out <= 64 is no slab layer: its entry point hands it to the 64-channel path unchanged.
+constexpr int SLAB_ROWS = 64;
+constexpr int SLAB_MAX = 65535;
+__host__ __device__ static inline int slab_count(int c_out) { return (c_out + SLAB_ROWS - 1) / SLAB_ROWS; }
+__host__ __device__ static inline int slab_first(int s) { return s * SLAB_ROWS; }
+__host__ __device__ static inline int slab_rows(int s, int c_out)
+{
+    const int n = c_out - slab_first(s);
+    return n < SLAB_ROWS ? n : SLAB_ROWS;
+}
+
 // chain step m, half h -> the link's input channel and tap (tap >= KK = kh kw: no link of the chain, its weight is 0)
 __device__ __forceinline__ void any_link(int m, int h, int npair, int c_in, int KK, int &ci, int &tap)
 {
@@ -141,6 +156,22 @@ __device__ __forceinline__ void any_consts_to_lds(float *taus, float *sb, float 
     for (int i = tid; i < (WLDS ? nsteps : nwl) * 64 * MT; i += THREADS) wl[i] = wperm[i];
 }
 
+// the same for ONE SLAB of a wider layer (two M tiles on chip, nmt of them real): bias of the slab's nrow channels from co0 on,
+// and the slab's columns of the layer's permutation (wps = wperm at the slab's first column, gmt M tiles per step in memory)
+// re-packed to two per step; a column beyond the layer's last M tile does not exist in memory and is never read
+template <bool WLDS, int THREADS>
+__device__ __forceinline__ void any_consts_to_lds_slab(float *taus, float *sb, float *wl, const float *__restrict__ tau4,
+                                                       const float *__restrict__ bias, const float *__restrict__ wps, int c_in,
+                                                       int co0, int nrow, int nmt, int gmt, int nsteps, int nwl, int tid)
+{
+    for (int i = tid; i < 4 * c_in; i += THREADS) taus[i] = tau4[i];
+    if (tid < 64) sb[tid] = (bias && tid < nrow) ? bias[co0 + tid] : 0.0f;
+    for (int i = tid; i < (WLDS ? nsteps : nwl) * 128; i += THREADS) {
+        const int m = i >> 7, mtl = (i >> 6) & 1;
+        wl[i] = mtl < nmt ? wps[((long)m * gmt + mtl) * 64 + (i & 63)] : 0.0f;
+    }
+}
+
 template <int NM>
 struct any_acc {
     f32x16 t[NM];
@@ -148,11 +179,12 @@ struct any_acc {
 
 // NM chains (M tiles mt0 .. mt0 + NM - 1 of MT) of the 32 conv pixels whose lane-j pixel has its first tap at img[base0]: rows of
 // img are RS floats apart, channels CHS; one B operand read per step for all NM.  sb: bias; wl / wperm: the permuted weights in LDS
-// (steps below nwl; WLDS: all) / in memory
-template <int NM, int MT, bool WLDS>
+// (steps below nwl; WLDS: all) / in memory.  SLAB: wperm in MEMORY has gmt M tiles per step, not MT (a slab of a wider layer
+// reads its MT columns of the layer's permutation: wperm then points at the slab's first column); the LDS copy has MT
+template <int NM, int MT, bool WLDS, bool SLAB = false>
 __device__ __forceinline__ any_acc<NM> any_chain(const float *img, int RS, int CHS, int base0, const float *sb, const float *wl,
                                                  const float *__restrict__ wperm, int nwl, int npair, int nsteps, int c_in, int kh,
-                                                 int kw, int lane, int hh, int mt0)
+                                                 int kw, int lane, int hh, int mt0, int gmt = MT)
 {
     const float *bp = img + base0 + hh * CHS;
     any_acc<NM> acc;
@@ -163,6 +195,7 @@ __device__ __forceinline__ any_acc<NM> any_chain(const float *img, int RS, int C
     auto wa = [&](int m, int n) -> float {
         const int o = (m * MT + mt0 + n) * 64 + lane;
         if constexpr (WLDS) return wl[o];
+        else if constexpr (SLAB) return m < nwl ? wl[o] : wperm[(m * gmt + mt0 + n) * 64 + lane];
         else return m < nwl ? wl[o] : wperm[o];
     };
     int m = 0, off = 0, kx = 0, ky = 0;

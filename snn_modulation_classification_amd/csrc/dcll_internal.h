@@ -165,6 +165,14 @@ __attribute__((visibility("hidden")))
 int dcll_launch_bwd_wgrad_wide(const dcll_conv_desc *d, const float *gvf, const float *eps1, float *part, int32_t B,
                                long *nchunk, hipStream_t st);
 
+// k_bwd_wgrad_slab (dcll_bwd_slab.hip): the same for a plain conv layer with more than 64 output channels, in slabs of 64
+// (blockIdx.z; the slab rule: dcll_any_shared.h).  _check and launcher as for k_bwd_wgrad_wide; layers of at most 64 output
+// channels never reach them (dcll_conv_lif_backward_slab hands those to the _wide path)
+__attribute__((visibility("hidden"))) int dcll_bwd_wgrad_slab_check(const dcll_conv_desc *d, const char *who);
+__attribute__((visibility("hidden")))
+int dcll_launch_bwd_wgrad_slab(const dcll_conv_desc *d, const float *gvf, const float *eps1, float *part, int32_t B,
+                               long *nchunk, hipStream_t st);
+
 // k_seq_any_wprep (dcll_seq_any.hip): the weights of a plain conv layer in MFMA fragment order, wperm[m][mt][lane], 64 MT floats
 // per chain step (any_chain_steps(), dcll_any_shared.h) — the one permutation of k_lif_seq_any / k_lif_step_any (MT = 1) and of
 // k_lif_seq_wide / k_lif_seq_band / k_lif_seq_tile.  note: the launch goes into the launch log (the MT = 1 entry points; the others

@@ -723,17 +723,20 @@ class Conv2dDCLLlayer(nn.Module):
         return ops.step_w3_supported(desc) and ops.backward_w3_supported(desc)
 
     # -- the fused path of any plain conv layer (k_lif_seq_any, ABI 8): opt-in, beside sequence_kind / forward_sequence ---
-    def sequence_any_supported(self, wide=False, bands=None, tiles=None):
+    def sequence_any_supported(self, wide=False, bands=None, tiles=None, slabs=None):
         """True if dcll_conv_lif_sequence_any serves this layer: built inside the fused step (not _general()), no active
         lc_dropout, time constants constant over (H, W), and the library's own predicate (plain conv, c_out <= 32, kernel up
         to 16x16, the per-sample working set within a workgroup's LDS).  wide=True: dcll_conv_lif_sequence_wide's predicate
         (c_out <= 64) instead.  bands = an int: dcll_conv_lif_sequence_bands' predicate at that band count (0: at some band
         count) instead of either.  tiles = (ty, tx): dcll_conv_lif_sequence_tiles' predicate at that tile plan ((0, 0): at some
-        plan) instead of all three."""
+        plan) instead of all three.  slabs = (ty, tx): dcll_conv_lif_sequence_slabs' predicate (any c_out) at that plan instead of all
+        four."""
         i = self.i2h
         if i._general() or self.dropout_active() or i.tau_per_channel() is None:
             return False
         desc = i.make_desc(self.im_dims, self.pooling, self.target_size, self.output_layer)
+        if slabs is not None:
+            return ops.sequence_slabs_supported(desc, slabs)
         if tiles is not None:
             return ops.sequence_tiles_supported(desc, tiles)
         if bands is not None:
@@ -741,7 +744,7 @@ class Conv2dDCLLlayer(nn.Module):
         return ops.sequence_wide_supported(desc) if wide else ops.sequence_any_supported(desc)
 
     def forward_sequence_any(self, x_packed, T, B, want_spikes=True, want_pv=True, want_v=False, buffers=None,
-                             batch_slice=None, wide=False, bands=None, tiles=None):
+                             batch_slice=None, wide=False, bands=None, tiles=None, slabs=None):
         """All T steps in one launch of k_lif_seq_any (wide=True: through dcll_conv_lif_sequence_wide — k_lif_seq_wide for
         33-64 output channels).  x_packed: (T,B,C_in,ceil(H*W/32)) int32 spike planes
         (ops.pack_spike_planes).  Neuron state as in forward_sequence (rows batch_slice.. of it for a chunk of a batch).
@@ -749,11 +752,14 @@ class Conv2dDCLLlayer(nn.Module):
         bands = an int: through dcll_conv_lif_sequence_bands with that many workgroups per sample (k_lif_seq_band; 0: the
         library's rule; 1: dcll_conv_lif_sequence_wide itself); None: the calls above.
         tiles = (ty, tx): through dcll_conv_lif_sequence_tiles with ty x tx workgroups per sample (k_lif_seq_tile; (0, 0): the
-        library's rule; (ty, 1): dcll_conv_lif_sequence_bands itself); wins over bands and wide."""
+        library's rule; (ty, 1): dcll_conv_lif_sequence_bands itself); wins over bands and wide.
+        slabs = (ty, tx): through dcll_conv_lif_sequence_slabs — a layer of more than 64 output channels in slabs of 64, ty x tx
+        tiles per (sample, slab) (k_lif_seq_slab; (0, 0): the library's rule); at most 64 channels: the tiles call itself; wins
+        over tiles, bands and wide."""
         i2h = self.i2h
-        if not self.sequence_any_supported(wide=wide, bands=bands, tiles=tiles):
+        if not self.sequence_any_supported(wide=wide, bands=bands, tiles=tiles, slabs=slabs):
             raise ops._lib.DCLLUnsupported('dcll_conv_lif_sequence_%s does not serve this layer'
-                                           % ('tiles' if tiles is not None else 'bands' if bands is not None else 'wide' if wide
+                                           % ('slabs' if slabs is not None else 'tiles' if tiles is not None else 'bands' if bands is not None else 'wide' if wide
                                               else 'any'))
         if batch_slice is None:
             if i2h.state is None or i2h.state.eps0.shape[0] != B:
@@ -768,6 +774,8 @@ class Conv2dDCLLlayer(nn.Module):
                 call = lambda *a, **kw: ops.conv_lif_sequence_bands(*a, bands=bands, **kw)
             if tiles is not None:
                 call = lambda *a, **kw: ops.conv_lif_sequence_tiles(*a, tiles=tiles, **kw)
+            if slabs is not None:
+                call = lambda *a, **kw: ops.conv_lif_sequence_slabs(*a, slabs=slabs, **kw)
             return call(desc, x_packed, i2h.weight, i2h.bias, i2h.tau_per_channel(), st.eps0, st.eps1,
                         st.arp if len(st) > 2 else None, T, B, want_spikes=want_spikes, want_pv=want_pv, want_v=want_v,
                         out=buffers)
@@ -1200,6 +1208,8 @@ class DCLLBase(nn.Module):
 
     wide_learning_path = False      # _learn_tail: dcll_conv_lif_backward_wide[_open] (k_bwd_wgrad_wide: layers of up to 64 channels)
 
+    slab_learning_path = False      # _learn_tail: dcll_conv_lif_backward_slab[_open] (k_bwd_wgrad_slab: layers of any width, 64-channel slabs)
+
     w3_learning_path = False        # _learn_tail: dcll_conv_lif_backward_w3[_open] (k_bwd_wgrad_w3); set by ConvNetwork.w3_step_path
     w3_first_wgrad = False          # with w3_learning_path: dcll_conv_lif_backward_w3f[_open] (the c_in 1 layer on k_bwd_wgrad_w3f);
                                     # set by ConvNetwork.w3_first_wgrad
@@ -1229,6 +1239,15 @@ class DCLLBase(nn.Module):
             return False
         return ops.backward_wide_supported(L.i2h.make_desc(L.im_dims, L.pooling, L.i2o.weight.shape[0], L.output_layer))
 
+    def backward_slab_supported(self):
+        """True if this slice's native learning step can take its weight gradient from dcll_conv_lif_backward_slab: as
+        backward_wide_supported with any number of output channels (ops.backward_slab_supported; c_out <= 64 runs the wide path's
+        kernels)."""
+        L = self.dclllayer
+        if not isinstance(L, Conv2dDCLLlayer) or L.i2h._general():
+            return False
+        return ops.backward_slab_supported(L.i2h.make_desc(L.im_dims, L.pooling, L.i2o.weight.shape[0], L.output_layer))
+
     def step_any_supported(self):
         """True if this slice's layer steps can run on k_lif_step_any (Conv2dDCLLlayer.step_any_supported)."""
         L = self.dclllayer
@@ -1250,7 +1269,7 @@ class DCLLBase(nn.Module):
         dcll_conv_lif_backward into the parameters' .grad.  `open_reduce`: the weight gradient's last reduction is left to
         the caller's ops.grad_reduce_adam (self._learn_bufs['grads']['parts']); `defer_backward` (a list, with open_reduce): the
         backward is not launched here but appended for ops.conv_lif_backward_open_multi (all slices' dv in one launch) — with
-        any_learning_path, wide_learning_path or w3_learning_path the slice's own open call is launched at once instead.
+        any_learning_path, wide_learning_path, slab_learning_path or w3_learning_path the slice's own open call is launched at once instead.
         -> loss (1,) device tensor or None"""
         L = self.dclllayer
         i2h = L.i2h
@@ -1285,7 +1304,7 @@ class DCLLBase(nn.Module):
                                   want_out=L.output_layer, out=gb, open_reduce=open_reduce,
                                   defer=defer_backward if open_reduce else None, any_path=self.any_learning_path,
                                   w3_path=self.w3_learning_path, w3_first=self.w3_first_wgrad, w3_dv=self.w3_dv,
-                                  wide_path=self.wide_learning_path)
+                                  wide_path=self.wide_learning_path, slab_path=self.slab_learning_path)
         return loss
 
     def _grads_into_slab(self):

@@ -307,6 +307,7 @@ class ConvNetwork(torch.nn.Module):
             walk(s.__dict__.get('_learn_bufs', {}))
             sig.append(bool(s.any_learning_path))
             sig.append(bool(s.wide_learning_path))
+            sig.append(bool(s.slab_learning_path))
             sig.append(bool(L.i2h.any_step_path))
             sig.append(bool(L.i2h.wide_step_path))
             sig.append((bool(s.w3_learning_path), bool(L.i2h.w3_step_path), bool(s.w3_first_wgrad), bool(s.w3_dv)))
@@ -895,6 +896,8 @@ class ConvNetwork(torch.nn.Module):
             raise ops._lib.DCLLUnsupported('any_learning_path cannot be combined with w3_step_path')
         if on and any(s.wide_learning_path for s in self.dcll_slices):
             raise ops._lib.DCLLUnsupported('any_learning_path cannot be combined with wide_learning_path')
+        if on and any(s.slab_learning_path for s in self.dcll_slices):
+            raise ops._lib.DCLLUnsupported('any_learning_path cannot be combined with slab_learning_path')
         if on and not self.backward_any_supported():
             raise ops._lib.DCLLUnsupported('dcll_conv_lif_backward_any does not serve every layer of this network')
         for s in self.dcll_slices:
@@ -919,10 +922,38 @@ class ConvNetwork(torch.nn.Module):
         on = bool(on)
         if on and (self.w3_step_path or any(s.any_learning_path for s in self.dcll_slices)):
             raise ops._lib.DCLLUnsupported('wide_learning_path cannot be combined with w3_step_path / any_learning_path')
+        if on and any(s.slab_learning_path for s in self.dcll_slices):
+            raise ops._lib.DCLLUnsupported('wide_learning_path cannot be combined with slab_learning_path')
         if on and not self.backward_wide_supported():
             raise ops._lib.DCLLUnsupported('dcll_conv_lif_backward_wide does not serve every layer of this network')
         for s in self.dcll_slices:
             s.wide_learning_path = on           # (part of _graph_signature: a captured timestep of the other path is retaken)
+
+    # -- the MFMA weight gradient of layers of ANY width, in slabs of 64 output channels (k_bwd_wgrad_slab): opt-in, beside the others --
+    def backward_slab_supported(self):
+        """True if every slice is served by dcll_conv_lif_backward_slab (DCLLBase.backward_slab_supported)."""
+        return all(s.backward_slab_supported() for s in self.dcll_slices)
+
+    @property
+    def slab_learning_path(self):
+        """True: every slice's learning step takes its weight gradient from dcll_conv_lif_backward_slab — k_bwd_wgrad_slab (fp32
+        MFMA, one slab of 64 output channels per workgroup) for the layers of more than 64 output channels that a netscale above
+        2 makes, k_bwd_wgrad_wide / k_bwd_wgrad_any for the narrower ones — instead of the default dispatch.  The step's structure
+        is unchanged: layer kernels, tails, one dcll_grad_reduce_adam.  Default False; setting it on a network that is not fully
+        served, or together with w3_step_path, any_learning_path or wide_learning_path, raises DCLLUnsupported and leaves it off;
+        switching it off is always allowed."""
+        return all(s.slab_learning_path for s in self.dcll_slices)
+
+    @slab_learning_path.setter
+    def slab_learning_path(self, on):
+        on = bool(on)
+        if on and (self.w3_step_path or any(s.any_learning_path or s.wide_learning_path or s.w3_learning_path for s in self.dcll_slices)):
+            raise ops._lib.DCLLUnsupported('slab_learning_path cannot be combined with w3_step_path / any_learning_path / '
+                                           'wide_learning_path')
+        if on and not self.backward_slab_supported():
+            raise ops._lib.DCLLUnsupported('dcll_conv_lif_backward_slab does not serve every layer of this network')
+        for s in self.dcll_slices:
+            s.slab_learning_path = on           # (part of _graph_signature: a captured timestep of the other path is retaken)
 
     # -- the MFMA per-step forward of any plain conv layer (k_lif_step_any, ABI 10): opt-in, beside the default dispatch -------
     def step_any_supported(self):
@@ -1002,6 +1033,8 @@ class ConvNetwork(torch.nn.Module):
             raise ops._lib.DCLLUnsupported('w3_step_path cannot be combined with any_step_path / any_learning_path')
         if on and any(s.wide_learning_path for s in self.dcll_slices):
             raise ops._lib.DCLLUnsupported('w3_step_path cannot be combined with wide_learning_path')
+        if on and any(s.slab_learning_path for s in self.dcll_slices):
+            raise ops._lib.DCLLUnsupported('w3_step_path cannot be combined with slab_learning_path')
         if on and any(s.dclllayer.i2h.wide_step_path for s in self.dcll_slices):
             raise ops._lib.DCLLUnsupported('w3_step_path cannot be combined with wide_step_path')
         if on and not self.w3_step_supported():
@@ -1049,16 +1082,18 @@ class ConvNetwork(torch.nn.Module):
             s.w3_dv = on
 
     # -- the fused path of any plain conv network (k_lif_seq_any, ABI 8): opt-in, beside test_sequence ---------------------
-    def sequence_any_supported(self, wide=False, bands=None, tiles=None):
+    def sequence_any_supported(self, wide=False, bands=None, tiles=None, slabs=None):
         """True if every layer is served by dcll_conv_lif_sequence_any (Conv2dDCLLlayer.sequence_any_supported): any plain
         conv spec with at most 32 output channels per layer whose per-sample working set fits a workgroup's LDS —
         mnist_conv.yaml, radio_ml_conv.yaml on any small plane.  Independent of sequence_supported().  wide=True: served by
         dcll_conv_lif_sequence_wide, up to 64 output channels per layer (the same specs at --netscale up to 2).  bands = an
         int: served by dcll_conv_lif_sequence_bands at that band count (0: the library's rule) — up to 64 output channels, and
         planes whose per-sample state is beyond one workgroup's LDS.  tiles = (ty, tx): served by dcll_conv_lif_sequence_tiles at
-        that tile plan ((0, 0): the library's rule) — planes and layers too wide for any band count; wins over bands and wide."""
+        that tile plan ((0, 0): the library's rule) — planes and layers too wide for any band count; wins over bands and wide.  slabs = (ty, tx): served by
+        dcll_conv_lif_sequence_slabs at that tile plan ((0, 0): the library's rule) — layers of ANY number of output channels, in
+        slabs of 64 (the specs at --netscale 3, 4, ...); wins over tiles, bands and wide."""
         return all(isinstance(s.dclllayer, Conv2dDCLLlayer) and
-                   s.dclllayer.sequence_any_supported(wide=wide, bands=bands, tiles=tiles)
+                   s.dclllayer.sequence_any_supported(wide=wide, bands=bands, tiles=tiles, slabs=slabs)
                    for s in self.dcll_slices)
 
     def _any_input_planes(self, x):
@@ -1083,7 +1118,7 @@ class ConvNetwork(torch.nn.Module):
         return ops.pack_spike_planes(x.to(torch.float32).reshape(T, B, C, H * W))
 
     @torch.no_grad()
-    def test_sequence_any(self, x, collect=True, keep_spikes=False, wide=False, bands=None, tiles=None):
+    def test_sequence_any(self, x, collect=True, keep_spikes=False, wide=False, bands=None, tiles=None, slabs=None):
         """Equivalent of `for t in range(T): net.test(x[t])` on the fused kernel of ANY plain conv layer (k_lif_seq_any):
         x = dense spike planes (T,B,C,H,W) on the device (any float or bool dtype; packed on the device), the same planes
         already packed ((T,B,C,ceil(H*W/32)) int32), or cell indices (T,B) for a one-channel first layer.  Every layer runs
@@ -1097,10 +1132,13 @@ class ConvNetwork(torch.nn.Module):
         (k_lif_seq_band; 0: the library's rule per layer; 1: dcll_conv_lif_sequence_wide itself); None: the calls above.
         tiles = (ty, tx): every layer call goes to dcll_conv_lif_sequence_tiles with ty x tx workgroups per sample
         (k_lif_seq_tile; (0, 0): the library's rule per layer; (ty, 1): dcll_conv_lif_sequence_bands itself); it wins over
-        bands and wide."""
-        if not self.sequence_any_supported(wide=wide, bands=bands, tiles=tiles):
+        bands and wide.
+        slabs = (ty, tx): every layer call goes to dcll_conv_lif_sequence_slabs — layers of more than 64 output channels in slabs of
+        64 with ty x tx tiles per (sample, slab) (k_lif_seq_slab; (0, 0): the library's rule per layer), narrower layers through
+        dcll_conv_lif_sequence_tiles itself; it wins over tiles, bands and wide."""
+        if not self.sequence_any_supported(wide=wide, bands=bands, tiles=tiles, slabs=slabs):
             raise ops._lib.DCLLUnsupported('dcll_conv_lif_sequence_%s does not serve every layer of this network; '
-                                           'use net.test(x[t])' % ('tiles' if tiles is not None else 'bands' if bands is not None
+                                           'use net.test(x[t])' % ('slabs' if slabs is not None else 'tiles' if tiles is not None else 'bands' if bands is not None
                                                                    else 'wide' if wide else 'any'))
         T, B = int(x.shape[0]), int(x.shape[1])
         dev = x.device
@@ -1115,7 +1153,7 @@ class ConvNetwork(torch.nn.Module):
                 if s.dclllayer.i2h.state is None or s.dclllayer.i2h.state.eps0.shape[0] != B:
                     s.dclllayer.i2h.init_state(B, s.dclllayer.im_dims)
             parts = [self._sequence_any_chunk(x[:, b0:min(B, b0 + chunk)], T, min(B, b0 + chunk) - b0, b0, keep_spikes, wide,
-                                              bands, tiles)
+                                              bands, tiles, slabs)
                      for b0 in range(0, B, chunk)]
             cat = lambda key, dim: [None if parts[0][key][i] is None else torch.cat([p[key][i] for p in parts], dim)
                                     for i in range(self.num_layers)]
@@ -1125,7 +1163,7 @@ class ConvNetwork(torch.nn.Module):
             if keep_spikes:
                 res['spikes'] = cat('spikes', 1)
         else:
-            res = self._sequence_any_chunk(x, T, B, None, keep_spikes, wide, bands, tiles)
+            res = self._sequence_any_chunk(x, T, B, None, keep_spikes, wide, bands, tiles, slabs)
         if collect:
             for i, s in enumerate(self.dcll_slices):
                 L = s.dclllayer
@@ -1133,7 +1171,7 @@ class ConvNetwork(torch.nn.Module):
                                       numel=B * L.out_channels * int(np.prod(L.output_shape)), vote=res['vote'][i])
         return res
 
-    def _sequence_any_chunk(self, x, T, B, batch_slice, keep_spikes, wide=False, bands=None, tiles=None):
+    def _sequence_any_chunk(self, x, T, B, batch_slice, keep_spikes, wide=False, bands=None, tiles=None, slabs=None):
         """All layers over all T steps for B samples (the whole batch, or rows batch_slice.. of every layer's state)."""
         for s in self.dcll_slices:
             i2h = s.dclllayer.i2h
@@ -1149,7 +1187,7 @@ class ConvNetwork(torch.nn.Module):
             last = (i == self.num_layers - 1)
             spk, pv, _ = L.forward_sequence_any(cur, T, B, want_spikes=(not last) or keep_spikes, want_pv=True,
                                                 buffers=scratch.setdefault(i, {}), batch_slice=batch_slice, wide=wide, bands=bands,
-                                                tiles=tiles)
+                                                tiles=tiles, slabs=slabs)
             res['lowhigh'].append(ops.pv_lowhigh(pv.reshape(T, -1), T, s.iter) if s.collect_stats else None)
             if keep_spikes:
                 res['spikes'].append(spk)

@@ -304,13 +304,26 @@ def backward_wide_supported(desc):
     return backward_wide_lds(desc) > 0
 
 
+def backward_slab_lds(desc):
+    """LDS bytes per workgroup of k_bwd_wgrad_slab on this layer (c_out <= 64: backward_wide_lds, the path that serves it), 0 = the
+    layer is not served (dcll_conv_lif_backward_slab_lds)."""
+    return int(_lib.get().dcll_conv_lif_backward_slab_lds(ctypes.byref(desc)))
+
+
+def backward_slab_supported(desc):
+    """True if conv_lif_backward(slab_path=True) serves the layer: a plain conv of any c_out (slabs of 64 output channels), a kernel
+    up to 16x16 and a smallest working set (one column tile's padded eps1 channels + a slab's rows of the sample's dv plane) within
+    the 160 KiB of LDS."""
+    return backward_slab_lds(desc) > 0
+
+
 BWD_ANY_MAX_CHUNKS = 256        # batch chunks (partial rows) of k_bwd_wgrad_any, at most
 BWD_W3F_PB = 128                # pixels of a job of k_bwd_wgrad_w3f (the flattened B x h w stream): at most one partial row per job
 W3_FIRST_WGRAD, W3_DV = 1, 2    # flag bits of dcll_conv_lif_backward_w3_ex[_open] (DCLL_W3_FIRST_WGRAD, DCLL_W3_DV)
 
 
 def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want_out, out=None, open_reduce=False, defer=None,
-                      any_path=False, w3_path=False, w3_first=False, w3_dv=False, wide_path=False):
+                      any_path=False, w3_path=False, w3_first=False, w3_dv=False, wide_path=False, slab_path=False):
     """Gradients of one layer step (dcll_conv_lif_backward) -> (dW, db, d_outW, d_outb).  `out`: optional dict with
     preallocated 'dW', 'db', 'd_outW', 'd_outb', 'bwd_scratch' (the learning loop writes into the parameters' .grad).
     `open_reduce`: dcll_conv_lif_backward_open — dW / db are NOT written yet; the partial rows of the weight gradient stay
@@ -328,7 +341,12 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
     k_bwd_dv); the scratch size is unchanged.
     `wide_path`: dcll_conv_lif_backward_wide[_open] — the weight gradient of a plain conv layer with up to 64 output channels on
     k_bwd_wgrad_wide (fp32 MFMA, two 32-row M tiles; backward_wide_supported); a layer with c_out <= 32 runs the `any_path` kernels,
-    same bits and launch log.  `defer` as for `any_path`; combined with `any_path` or `w3_path` it raises."""
+    same bits and launch log.  `defer` as for `any_path`; combined with `any_path` or `w3_path` it raises.
+    `slab_path`: dcll_conv_lif_backward_slab[_open] — the weight gradient of a plain conv layer of ANY width on k_bwd_wgrad_slab (fp32
+    MFMA, one slab of 64 output channels per workgroup; backward_slab_supported); a layer with c_out <= 64 runs the `wide_path`
+    kernels, same bits and launch log.  `defer` as for `any_path`; combined with any other path it raises."""
+    if slab_path and (any_path or w3_path or wide_path):
+        raise ValueError("conv_lif_backward(slab_path=True) cannot be combined with any_path=True, w3_path=True or wide_path=True")
     if wide_path and (any_path or w3_path):
         raise ValueError("conv_lif_backward(wide_path=True) cannot be combined with any_path=True or w3_path=True")
     if w3_path and any_path:
@@ -360,7 +378,7 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
     jobs = B * max(1, (desc.h // 16) * (desc.w // 16))
     per_chunk = desc.c_out * ((desc.c_in // desc.groups) * desc.kh * desc.kw + 1)
     nchunk = min(jobs, 1024 if desc.c_in == 1 else 256)      # (first layer: 128-thread workgroups, 6 KB partial rows)
-    if any_path or wide_path:
+    if any_path or wide_path or slab_path:
         nchunk = min(B, BWD_ANY_MAX_CHUNKS)
     if w3_path and desc.c_in == 64:
         nchunk = min(-(-B * desc.h * desc.w // 128), BWD_ANY_MAX_CHUNKS)       # (k_bwd_wgrad_w3: one row per 128-pixel block)
@@ -383,10 +401,12 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
     fn = "dcll_conv_lif_backward_w3f" if w3_first else "dcll_conv_lif_backward_w3" if w3_path else "dcll_conv_lif_backward_any" if any_path else "dcll_conv_lif_backward"
     if wide_path:
         fn = "dcll_conv_lif_backward_wide"
+    if slab_path:
+        fn = "dcll_conv_lif_backward_slab"
     flags = ()
     if w3_dv:       # (the flag-word entry points; without w3_dv the calls above are made as before)
         fn, flags = "dcll_conv_lif_backward_w3_ex", (W3_DV | (W3_FIRST_WGRAD if w3_first else 0),)
-    if defer is not None and not any_path and not w3_path and not wide_path:       # (open form, launched later with other layers': conv_lif_backward_open_multi)
+    if defer is not None and not any_path and not w3_path and not wide_path and not slab_path:       # (open form, launched later with other layers': conv_lif_backward_open_multi)
         item = _lib.BwdItem(ctypes.pointer(desc), ptr(eps1), ptr(v), ptr(pv_pooled), ptr(gp_), ptr(go_), ptr(gpv_), ptr(gv_),
                             ptr(i2o_W), ptr(d_outW), ptr(d_outb), ptr(scratch), n_scratch, B, 0, None, 0, 0)
         defer.append(dict(item=item, out=out, desc=desc, dW=dW, db=db, scratch=scratch,
@@ -1071,6 +1091,53 @@ def conv_lif_sequence_tiles(desc, spk_in, W, b, tau4, eps0, eps1, arp, T, B, wan
                                   desc, spk_in, W, b, tau4, eps0, eps1, arp, T, B, want_spikes, want_pv, want_v, out)
     if out is not None:
         mine["tile_scratch"] = out["w_scratch"]
+    return res
+
+
+def sequence_slabs_plan(desc, B, slabs=(0, 0)):
+    """The tile plan dcll_conv_lif_sequence_slabs runs on this layer at batch B: (pooled-row bounds, pooled-column bounds), two
+    lists of NY + 1 and NX + 1 ints, None = refused.  slabs = (0, 0): the library's rule (the fitting plan of the fewest tiles,
+    from one tile up — derived from the LDS formula alone, not measured); (ty, tx): exactly that plan, 1 x 1 and N x 1 included.
+    c_out <= 64: sequence_tiles_plan's answer (host-only: no device is touched)."""
+    lib = _lib.get()
+    ty, tx = _tiles_pair(slabs)
+    nn = (ctypes.c_int32 * 2)()
+    if int(lib.dcll_conv_lif_sequence_slabs_plan(ctypes.byref(desc), int(B), ty, tx, nn, None, None)) <= 0:
+        return None
+    by, bx = (ctypes.c_int32 * (nn[0] + 1))(), (ctypes.c_int32 * (nn[1] + 1))()
+    lib.dcll_conv_lif_sequence_slabs_plan(ctypes.byref(desc), int(B), ty, tx, nn, by, bx)
+    return list(by), list(bx)
+
+
+def sequence_slabs_lds(desc, slabs=(0, 0)):
+    """LDS bytes of the largest tile of this plan — the tile formula with a slab's 64 channels in place of c_out — 0 = refused
+    (dcll_conv_lif_sequence_slabs_lds; host-only; c_out <= 64: sequence_tiles_lds)."""
+    ty, tx = _tiles_pair(slabs)
+    return int(_lib.get().dcll_conv_lif_sequence_slabs_lds(ctypes.byref(desc), ty, tx))
+
+
+def sequence_slabs_supported(desc, slabs=(0, 0)):
+    """True if dcll_conv_lif_sequence_slabs serves the layer with this plan ((0, 0): with some plan): a plain conv of any c_out
+    (slabs of 64 output channels), a kernel up to 16x16 and the largest tile's working set within a workgroup's LDS."""
+    return sequence_slabs_lds(desc, slabs) > 0
+
+
+def conv_lif_sequence_slabs(desc, spk_in, W, b, tau4, eps0, eps1, arp, T, B, want_spikes=True, want_pv=True, want_v=False,
+                            out=None, slabs=(0, 0)):
+    """conv_lif_sequence_any through dcll_conv_lif_sequence_slabs: a layer of more than 64 output channels in slabs of 64, slabs =
+    (ty, tx) tiles per (sample, slab), each workgroup on a tile of the output plane and a slab of channels for all T
+    (k_lif_seq_slab; (0, 0) = the library's rule); a layer of at most 64 channels IS conv_lif_sequence_tiles(tiles=slabs).  Same
+    arguments, buffers and results; its one scratch buffer (permuted weights + the snapshot of eps0 / eps1) is kept in `out` under
+    'slab_scratch'."""
+    lib = _lib.get()
+    ty, tx = _tiles_pair(slabs)
+    if out is not None:             # (_conv_lif_sequence_call keeps its scratch under 'w_scratch': the siblings' buffer stays theirs)
+        out, mine = dict(out, w_scratch=out.get("slab_scratch")), out
+    call = lambda *a: lib.dcll_conv_lif_sequence_slabs(*(a[:-1] + (ty, tx, a[-1])))
+    res = _conv_lif_sequence_call(call, lambda d: lib.dcll_conv_lif_sequence_slabs_scratch(d, B), "dcll_conv_lif_sequence_slabs",
+                                  desc, spk_in, W, b, tau4, eps0, eps1, arp, T, B, want_spikes, want_pv, want_v, out)
+    if out is not None:
+        mine["slab_scratch"] = out["w_scratch"]
     return res
 
 

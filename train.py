@@ -110,6 +110,15 @@ def parse_args(argv=None):
                         '2.00x); NOT faster at netscale 2 on 128x128, B = 64: 2608.86-2617.72 -> 3135.56-3149.17, and at netscale 1 '
                         'on 48x48, B = 64: 68.86-69.88 -> 114.26-115.33 (the band rule; every tile plan is slower still) '
                         '(DESIGN 4.1g; experiments/seq_tile_timing.py)')
+    p.add_argument('--slab_sequence_path', type=int, nargs='*', default=None, metavar='N',
+                   help='opt in, TY TX: the test phase of a network without a geometry-specialised sequence kernel runs '
+                        'ConvNetwork.test_sequence_any(slabs=(TY, TX)) — dcll_conv_lif_sequence_slabs: layers of MORE than 64 output '
+                        'channels (--netscale above 2) in slabs of 64, TY x TX tiles per (sample, slab), each workgroup on a tile of '
+                        'the output plane and a slab of channels for all T (k_lif_seq_slab; both omitted or 0 0: the library\'s rule '
+                        'per layer, derived from the LDS formula alone); layers of at most 64 channels go through '
+                        'dcll_conv_lif_sequence_tiles itself.  One process only; ignored with a notice where the network is not '
+                        'served.  Wins over --any_sequence_path, --wide_sequence_path, --band_sequence_path and --tile_sequence_path.  '
+                        'Measured on an MI355X, T = 128, per-step loop -> the rule, ms per sequence, radio_ml_conv.yaml on 16x16: NOT faster at netscale 3 (B = 64: 111.59-112.27 -> 139.58-139.99; B = 512: 728.19-729.73 -> 1042.14-1043.32) and NOT faster at netscale 4 (B = 64: 179.94-180.63 -> 259.04-259.78; B = 512: 1258.31-1261.64 -> 1997.00-2004.39): the path is served, not quicker (DESIGN 4.1h; experiments/slab_timing.py)')
     p.add_argument('--any_learning_path', action='store_true',
                    help='opt in: every layer\'s weight gradient of the learning step runs on k_bwd_wgrad_any (fp32 MFMA; any '
                         'plain conv layer with c_out <= 32 and a kernel up to 16x16, which lifts the default path\'s 64-tap '
@@ -126,6 +135,13 @@ def parse_args(argv=None):
                         '10.51-10.55 -> 2.411-2.423 at B = 512 (4.3-4.4x); every layer\'s open backward call is faster, none slower; '
                         'the per-step forward of such layers stays on the default kernels (DESIGN 4.2d; '
                         'profiles/r20_bwd_wide_timing.txt; experiments/bwd_wide_timing.py)')
+    p.add_argument('--slab_learning_path', action='store_true',
+                   help='opt in: every layer\'s weight gradient of the learning step runs through dcll_conv_lif_backward_slab — '
+                        'k_bwd_wgrad_slab (fp32 MFMA, one slab of 64 output channels per workgroup) for layers of more than 64 output '
+                        'channels (--netscale above 2), k_bwd_wgrad_wide for 33-64, k_bwd_wgrad_any up to 32 — where '
+                        'ConvNetwork.backward_slab_supported() holds; ignored with a notice elsewhere and together with '
+                        '--any_learning_path / --wide_learning_path / --w3_step_path.  Measured on an MI355X against the same tree without the flag, five alternating fresh processes, min-max ms per net.learn timestep, radio_ml_conv.yaml on 16x16, T = 128: netscale 3: 15.55-15.57 -> 1.552-1.563 at B = 64 (9.9-10.0x), 42.04-42.09 -> 9.245-9.313 at B = 512 (4.5x); netscale 4: 27.45-27.49 -> 2.332-2.356 at B = 64 (11.7-11.8x), 74.35-74.56 -> 14.78-14.90 at B = 512 (5.0x); every layer\'s open backward call is faster, none slower; the votes of the free-running arms are NOT equal (another summation order under Adam); the forward of such layers stays on the default kernels (DESIGN 4.2f; '
+                        'experiments/slab_timing.py)')
     p.add_argument('--any_step_path', action='store_true',
                    help='opt in: every per-step layer call (net.test per timestep, every learning timestep) runs k_lif_step_any '
                         '(one fp32-MFMA launch with the traces and the pooling fused in; any plain conv layer with c_out <= 32 and '
@@ -235,6 +251,7 @@ def main(argv=None):
     _opt_in_w3_step(net, args)
     _opt_in_wide_step(net, args)
     _opt_in_wide_learning(net, args)
+    _opt_in_slab_learning(net, args)
     parallel.freeze_startup_heap()          # (a full GC pass over the start-up heap costs ~100 ms inside the T-loop)
 
     if not args.no_save:
@@ -276,7 +293,9 @@ def main(argv=None):
     use_bands = _opt_in_band_sequence(net, args, use_sequence, world)
     # --tile_sequence_path [TY TX]: the same through dcll_conv_lif_sequence_tiles; wins over the three above
     use_tiles = _opt_in_tile_sequence(net, args, use_sequence, world)
-    use_any = use_any or use_wide or use_bands is not None or use_tiles is not None
+    # --slab_sequence_path [TY TX]: the same through dcll_conv_lif_sequence_slabs (any number of output channels); wins over the four above
+    use_slabs = _opt_in_slab_sequence(net, args, use_sequence, world)
+    use_any = use_any or use_wide or use_bands is not None or use_tiles is not None or use_slabs is not None
 
     def evaluate_batch_any(samples, labels1h):
         """The per-step branch of evaluate_batch (host-encoded planes, reference test_radio_ml.py:142-146) with its T-loop replaced
@@ -288,7 +307,7 @@ def main(argv=None):
         net.reset()
         net.eval()
         net.test_sequence_any(torch.Tensor(spikes).to(pytorch_libdcll.device)[:T], wide=use_wide, bands=use_bands,
-                              tiles=use_tiles)
+                              tiles=use_tiles, slabs=use_slabs)
         return net.accuracy(torch.as_tensor(np.asarray(targets), dtype=torch.float32))
 
     def run_tests(step):
@@ -456,6 +475,29 @@ def _opt_in_tile_sequence(net, args, use_sequence, world=1):
     return None
 
 
+def _opt_in_slab_sequence(net, args, use_sequence, world=1):
+    """--slab_sequence_path [TY TX]: the tile plan per (sample, slab) ((0, 0): the library's rule) where the test phase runs
+    ConvNetwork.test_sequence_any(slabs=(TY, TX)) — the conditions of --tile_sequence_path with dcll_conv_lif_sequence_slabs'
+    predicate; None elsewhere, with a notice where the flag was given."""
+    t = getattr(args, 'slab_sequence_path', None)
+    if t is None:
+        return None
+    if len(t) not in (0, 2):
+        raise SystemExit('--slab_sequence_path takes no value or two (TY TX)')
+    slabs = (int(t[0]), int(t[1])) if t else (0, 0)
+    if use_sequence:
+        why = 'the network runs its geometry-specialised sequence kernels'
+    elif world > 1:
+        why = 'several ranks keep the sharded per-step evaluation'
+    elif min(slabs) < 0 or not net.sequence_any_supported(slabs=slabs):
+        why = 'dcll_conv_lif_sequence_slabs does not serve every layer of this network with %s' % (
+            '%d x %d tiles' % slabs if slabs != (0, 0) else 'any tile plan')
+    else:
+        return slabs
+    print('--slab_sequence_path ignored: ' + why)
+    return None
+
+
 def _opt_in_any_learning(net, args):
     """--any_learning_path: switch the network's learning step to k_bwd_wgrad_any where every slice is served."""
     if not args.any_learning_path:
@@ -477,6 +519,20 @@ def _opt_in_wide_learning(net, args):
         net.wide_learning_path = True
     else:
         print('--wide_learning_path ignored: dcll_conv_lif_backward_wide does not serve every layer of this network')
+
+
+def _opt_in_slab_learning(net, args):
+    """--slab_learning_path: switch the network's learning step to dcll_conv_lif_backward_slab (k_bwd_wgrad_slab for layers of more
+    than 64 output channels, the wide path's kernels below) where every slice is served and no other learning path is in effect."""
+    if not getattr(args, 'slab_learning_path', False):
+        return
+    if net.any_learning_path or net.wide_learning_path or net.w3_step_path:
+        print('--slab_learning_path ignored: another learning path (--any_learning_path / --wide_learning_path / --w3_step_path) '
+              'is in effect')
+    elif net.backward_slab_supported():
+        net.slab_learning_path = True
+    else:
+        print('--slab_learning_path ignored: dcll_conv_lif_backward_slab does not serve every layer of this network')
 
 
 def _opt_in_any_step(net, args):
@@ -555,9 +611,11 @@ def main_mnist(args):
     _opt_in_w3_step(net, args)
     _opt_in_wide_step(net, args)
     _opt_in_wide_learning(net, args)
+    _opt_in_slab_learning(net, args)
     use_wide = _opt_in_wide_sequence(net, args, net.sequence_supported())      # (the condition of --any_sequence_path below)
     use_bands = _opt_in_band_sequence(net, args, net.sequence_supported())
     use_tiles = _opt_in_tile_sequence(net, args, net.sequence_supported())
+    use_slabs = _opt_in_slab_sequence(net, args, net.sequence_supported())
     parallel.freeze_startup_heap()          # (a full GC pass over the start-up heap costs ~100 ms inside the T-loop)
     n_test = int(np.ceil(float(args.n_test_samples) / args.batch_size_test))
     if args.synthetic:
@@ -609,7 +667,9 @@ def main_mnist(args):
                 tx, ty = spikes_of(ts, tl, st_test)
                 net.reset()
                 net.eval()
-                if use_tiles is not None:
+                if use_slabs is not None:
+                    net.test_sequence_any(tx[:args.n_iters_test], slabs=use_slabs)
+                elif use_tiles is not None:
                     net.test_sequence_any(tx[:args.n_iters_test], tiles=use_tiles)
                 elif use_bands is not None:
                     net.test_sequence_any(tx[:args.n_iters_test], bands=use_bands)
