@@ -854,6 +854,44 @@ int dcll_conv_lif_step_wide(const dcll_conv_desc *d, const float *x, const float
                             float *out_p, float *out_o, float *out_pv, float *out_v, float *w_scratch, int32_t B, void *stream);
 
 /*
+ * Added under ABI 10 (DCLL_ABI_VERSION is unchanged: a caller detects these four symbols by symbol lookup) —
+ * dcll_conv_lif_step_wide for ANY number of output channels and any plane height (k_lif_step_slab, csrc/dcll_step_slab.hip): the
+ * same arguments with `int32_t bands` in front of B, the same results, alignment rule (4 bytes, w_scratch included) and
+ * DCLL_ERR_INVALID cases, and bands < 0 -> DCLL_ERR_INVALID.  Additions only: the default dispatch, dcll_conv_lif_step_any,
+ * dcll_conv_lif_step_wide, their launch logs and refusals ("c_out <= 32", "c_out <= 64" included) are unchanged.
+ * Served (else DCLL_ERR_UNSUPPORTED, before any launch): stride = dilation = groups = 1; any c_in and c_out (at most 65 535 slabs
+ * of 64 output channels); kh, kw <= 16; any padding, pooling and batch; and a plan whose bands fit the 160 KiB of LDS.
+ * Grid = B x NB x NS workgroups.  NS = ceil(c_out / 64) slabs: slab s owns the channels [64 s, min(64 s + 64, c_out)), two 32-row
+ * M tiles (a last slab of at most 32 rows: one; its second weight column is never read); rows at or beyond c_out are never
+ * stored.  NB bands of output rows; band k owns the pooled rows [k ph / NB, (k + 1) ph / NB) and the conv rows [C0, C1) of their
+ * pooling windows (the last band also those behind the last window of floor-mode pooling) — k_lif_seq_band's partition in h;
+ * no tiling in w.  LDS of a (band, slab) workgroup:
+ *   4 bytes x (c_in (C1 - C0 + kh - 1)(w + 2 pad_w) [the band's zero-padded eps1 rows] + (pooling != 1 ? 64 (C1 - C0) cw : 0)
+ *   [the slab's v plane of the pooling pass] + 64 [bias]).
+ * The plan: bands = N >= 1 -> NB = N (N > ph, or a band beyond the LDS: refused).  bands = 0 -> NB_fit = the smallest NB <= ph
+ * whose largest band fits (none: refused); units = 2 ceil(ch cw / 32); ns0 = min(ceil(units / 4), 256 / (B NS)); NB =
+ * max(NB_fit, min(ns0, ph)).  dcll_conv_lif_step_slab_plan (host only) returns NB and NS; dcll_conv_lif_step_slab_lds the bytes of
+ * the largest workgroup under the plan (0: not served); dcll_conv_lif_step_slab_scratch the floats of w_scratch, 128 per MFMA step
+ * of a chain and slab (0: not served), written as [slab][step][lane][2] by k_step_slab_wprep in front of the layer kernel on
+ * EVERY call.
+ * c_out <= 64, bands = 0 and a layer dcll_conv_lif_step_wide serves: the call IS that call — same kernels, launch log, bits and
+ * _lds value (_plan then answers NB = NS = 0) — so a network of mixed widths goes through one entry point.  Everything else that
+ * is served runs k_lif_step_slab, NS = 1 included.
+ * The traces advance in k_trace BEFORE the layer kernel (workgroups of a sample read each other's halo rows, every slab reads the
+ * same traces); the kernel stages them read-only.  Each chain is the pinned order, unsplit: v equals dcll_conv_lif_step bit for
+ * bit up to the sign of a zero; spikes, eps0, eps1 and arp bit for bit; pv within the sigmoid's 1e-4.  Nothing depends on NB.
+ * Launch log (R = refractory): "k_step_slab_wprep", "k_trace", then "k_lif_step_slab<R>" or "k_lif_step_slab<R> (pooling)".
+ */
+int64_t dcll_conv_lif_step_slab_lds(const dcll_conv_desc *d, int32_t B, int32_t bands);
+int64_t dcll_conv_lif_step_slab_scratch(const dcll_conv_desc *d);
+int dcll_conv_lif_step_slab_plan(const dcll_conv_desc *d, int32_t B, int32_t bands, int32_t *nb, int32_t *ns);
+int dcll_conv_lif_step_slab(const dcll_conv_desc *d, const float *x, const float *W, const float *b, const float *alpha,
+                            const float *tau_m, const float *alphas, const float *tau_s, float *eps0, float *eps1, float *arp,
+                            const float *i2o_W, const float *i2o_b, const float *out_W, const float *out_b, float *out_s,
+                            float *out_p, float *out_o, float *out_pv, float *out_v, float *w_scratch, int32_t bands, int32_t B,
+                            void *stream);
+
+/*
  * Added under ABI 10 (DCLL_ABI_VERSION is unchanged: a caller detects these two symbols by symbol lookup) — one layer step of a
  * (1,3) / 64-channel / (1,2)-pool layer of radio_ml_conv_ref.yaml in one MFMA launch (k_lif_step_w3, csrc/dcll_step_w3.hip):
  * dcll_conv_lif_step_any's arguments without w_scratch, dcll_conv_lif_step's results.  Additions only: the default dispatch, its

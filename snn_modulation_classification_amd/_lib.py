@@ -176,6 +176,10 @@ SIGNATURES = {
     "dcll_conv_lif_step_wide_lds": (_I64, [_DP]),
     "dcll_conv_lif_step_wide_scratch": (_I64, [_DP]),
     "dcll_conv_lif_step_wide": (_I32, [_DP] + [_P] * 20 + [_I32, _P]),
+    "dcll_conv_lif_step_slab_lds": (_I64, [_DP, _I32, _I32]),
+    "dcll_conv_lif_step_slab_scratch": (_I64, [_DP]),
+    "dcll_conv_lif_step_slab_plan": (_I32, [_DP, _I32, _I32, _IP, _IP]),
+    "dcll_conv_lif_step_slab": (_I32, [_DP] + [_P] * 20 + [_I32, _I32, _P]),
     "dcll_conv_lif_step_w3_lds": (_I64, [_DP]),
     "dcll_conv_lif_step_w3": (_I32, [_DP] + [_P] * 19 + [_I32, _P]),
     "dcll_conv_lif_backward_w3_lds": (_I64, [_DP]),

@@ -3400,6 +3400,55 @@ extern "C" int dcll_conv_lif_step_wide(const dcll_conv_desc *d, const float *x, 
     return DCLL_OK;
 }
 
+// added under ABI 10: the layer step of a plain conv layer of any number of output channels on k_lif_step_slab
+// (dcll_step_slab.hip) — k_step_slab_wprep, k_trace, the layer kernel over B x bands x slabs workgroups, the readouts of
+// dcll_conv_lif_step.  bands = 0: the plan's rule, N >= 1: exactly N bands.  A layer of at most 64 output channels that
+// dcll_conv_lif_step_wide serves, asked for with bands = 0, IS the call above (same kernels, launch log, bits).  Every check —
+// the plan, the launcher's layout and grid checks and its LDS reservation included — comes before the first launch.
+extern "C" int dcll_conv_lif_step_slab(const dcll_conv_desc *d, const float *x, const float *W, const float *b,
+                                       const float *alpha, const float *tau_m, const float *alphas, const float *tau_s,
+                                       float *eps0, float *eps1, float *arp, const float *i2o_W, const float *i2o_b,
+                                       const float *out_W, const float *out_b, float *out_s, float *out_p, float *out_o,
+                                       float *out_pv, float *out_v, float *w_scratch, int32_t bands, int32_t B, void *stream)
+{
+    const char *who = "dcll_conv_lif_step_slab";
+    if (B < 0) return fail(DCLL_ERR_INVALID, "negative batch", who);
+    if (bands < 0) return fail(DCLL_ERR_INVALID, "negative band count", who);
+    if (B == 0) return DCLL_OK;
+    if (dcll_step_slab_forwards(d, bands))
+        return dcll_conv_lif_step_wide(d, x, W, b, alpha, tau_m, alphas, tau_s, eps0, eps1, arp, i2o_W, i2o_b, out_W, out_b, out_s,
+                                       out_p, out_o, out_pv, out_v, w_scratch, B, stream);
+    int nb = 0, ns = 0;
+    int rc = dcll_step_slab_plan(d, B, bands, &nb, &ns, who);
+    if (rc) return rc;
+    if (!x || !W || !alpha || !tau_m || !alphas || !tau_s || !eps0 || !eps1 || !out_s || !out_pv || !w_scratch)
+        return fail(DCLL_ERR_INVALID, "null pointer", who);
+    if (d->refractory && !arp) return fail(DCLL_ERR_INVALID, "refractory layer needs arp", who);
+    if (d->output_layer && (!out_W || !out_o)) return fail(DCLL_ERR_INVALID, "output layer needs out_W and out_o", who);
+    hipStream_t st = (hipStream_t)stream;
+    int ch, cw, ph, pw;
+    conv_shape(d, &ch, &cw, &ph, &pw);
+    const int K = d->c_out * ph * pw;
+    // (the launcher's own checks and its LDS reservation, nothing launched: an error return never leaves half-advanced state)
+    rc = dcll_launch_step_slab(d, w_scratch, b, eps1, arp, out_s, out_pv, out_v, nb, ns, B, st, false);
+    if (rc) return rc;
+    if ((rc = dcll_launch_step_slab_wprep(d, W, w_scratch, st)) != DCLL_OK) return rc;
+    {       // workgroups of one sample read each other's halo rows and every slab reads the same traces: they advance BEFORE the kernel
+        const long per = (long)d->c_in * d->h * d->w, nin = per * B;
+        hipLaunchKernelGGL(k_trace, dim3(nblk(nin, 256) > 4096 ? 4096 : nblk(nin, 256)), dim3(256), 0, st, x, alpha, tau_m,
+                           alphas, tau_s, eps0, eps1, nin, per, d->tau_is_tensor);
+        HIP_CHECK_LAUNCH("k_trace");
+    }
+    rc = dcll_launch_step_slab(d, w_scratch, b, eps1, arp, out_s, out_pv, out_v, nb, ns, B, st, true);
+    if (rc) return rc;
+    if (i2o_W && out_p) {
+        rc = launch_readout(out_pv, i2o_W, i2o_b, out_p, B, K, d->target, st);
+        if (rc) return rc;
+    }
+    if (d->output_layer) return launch_readout(out_pv, out_W, out_b, out_o, B, K, d->target, st);
+    return DCLL_OK;
+}
+
 // added under ABI 10: the layer step of a (1,3) / 64-channel / (1,2)-pool layer on k_lif_step_w3 (dcll_step_w3.hip) — one
 // launch, then the readouts of dcll_conv_lif_step.  Every check — the launcher's form, grid and LDS checks and its LDS
 // reservation included — comes before the first launch; behind it only a launch itself can fail.

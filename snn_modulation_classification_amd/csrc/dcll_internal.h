@@ -204,6 +204,19 @@ int dcll_launch_step_wide(const dcll_conv_desc *d, const float *x, const float *
                           const float *tau_m, const float *alphas, const float *tau_s, float *eps0, float *eps1, float *arp,
                           float *out_s, float *out_pv, float *out_v, int ns, int32_t B, hipStream_t st, bool launch);
 
+// k_lif_step_slab (dcll_step_slab.hip): one MFMA layer step of a plain conv layer of any number of output channels (kernel up to
+// 16x16) in bands of rows and slabs of 64 channels.  _forwards: the call is dcll_conv_lif_step_wide's (c_out <= 64, bands == 0,
+// served there) and never reaches the rest; _plan: DCLL_OK with the bands and slabs of a call (bands == 0: the rule) or the
+// refusal with its message; _wprep: w_scratch in the kernel's order (128 floats per chain step and slab); the launcher with
+// launch == false only prepares (checks, LDS reservation).  The caller runs k_trace in front of the layer kernel
+__attribute__((visibility("hidden"))) bool dcll_step_slab_forwards(const dcll_conv_desc *d, int32_t bands);
+__attribute__((visibility("hidden")))
+int dcll_step_slab_plan(const dcll_conv_desc *d, int32_t B, int32_t bands, int *nb, int *ns, const char *who);
+__attribute__((visibility("hidden"))) int dcll_launch_step_slab_wprep(const dcll_conv_desc *d, const float *W, float *wperm, hipStream_t st);
+__attribute__((visibility("hidden")))
+int dcll_launch_step_slab(const dcll_conv_desc *d, const float *wperm, const float *b, const float *eps1, float *arp,
+                          float *out_s, float *out_pv, float *out_v, int nb, int ns, int32_t B, hipStream_t st, bool launch);
+
 // k_lif_step_w3 (dcll_step_w3.hip): one MFMA layer step of the layers dcll_seq_w3_geometry() serves.  _check: DCLL_OK or the
 // refusal with its message; _tiles: tiles per workgroup (8 or 4) for (descriptor, B); the launcher with launch == false only
 // prepares (checks, LDS reservation): called before the first launch of the entry point

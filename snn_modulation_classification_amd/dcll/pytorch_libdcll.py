@@ -293,6 +293,10 @@ class ContinuousConv2D(nn.Module):
     # instead; opt-in through ConvNetwork.wide_step_path, which asks step_wide_supported() first.  Set here directly the same
     # holds: a layer the library refuses raises, there is no fall-back
     wide_step_path = False
+    # _step: dcll_conv_lif_step_slab (k_lif_step_slab: any number of output channels, bands of rows x slabs of 64 channels; a
+    # layer dcll_conv_lif_step_wide serves runs that call's kernels) instead; opt-in through ConvNetwork.slab_step_path, which
+    # asks step_slab_supported() first.  Set here directly the same holds: a layer the library refuses raises, no fall-back
+    slab_step_path = False
 
     def _step(self, input, pooling=(1, 1), i2o=None, output_=None, out=None, stacked=None, finish=None, want_v=True,
               defer_ro=False):
@@ -311,7 +315,8 @@ class ContinuousConv2D(nn.Module):
                 None if i2o is None else i2o.weight, None if i2o is None else i2o.bias,
                 None if output_ is None else output_.weight, None if output_ is None else output_.bias, out=out,
                 q8=self.int8_weights(), stacked=stacked, finish=finish, want_v=want_v, defer_ro=defer_ro,
-                any_path=self.any_step_path, w3_path=self.w3_step_path, wide_path=self.wide_step_path)
+                any_path=self.any_step_path, w3_path=self.w3_step_path, wide_path=self.wide_step_path,
+                slab_path=self.slab_step_path)
 
     def _general(self):
         """True when the layer was built with an option outside the fused step (see _is_sigmoid)."""
@@ -710,6 +715,16 @@ class Conv2dDCLLlayer(nn.Module):
         if i._general() or i.int8_weights() is not None:
             return False
         return ops.step_wide_supported(i.make_desc(self.im_dims, self.pooling, self.target_size, self.output_layer))
+
+    # -- the MFMA per-step forward of layers of any number of output channels (k_lif_step_slab): opt-in through i2h.slab_step_path
+    def step_slab_supported(self):
+        """True if dcll_conv_lif_step_slab serves this layer's steps: as step_wide_supported with any number of output channels
+        and any plane height whose band plan fits a workgroup's LDS (ops.step_slab_supported; a layer dcll_conv_lif_step_wide
+        serves runs that call's kernels)."""
+        i = self.i2h
+        if i._general() or i.int8_weights() is not None:
+            return False
+        return ops.step_slab_supported(i.make_desc(self.im_dims, self.pooling, self.target_size, self.output_layer))
 
     # -- the MFMA per-step forward and weight gradient of the (1,3) / 64-channel layers (k_lif_step_w3, k_bwd_wgrad_w3) ------
     def w3_step_supported(self):
@@ -1257,6 +1272,11 @@ class DCLLBase(nn.Module):
         """True if this slice's layer steps can run on k_lif_step_wide (Conv2dDCLLlayer.step_wide_supported)."""
         L = self.dclllayer
         return isinstance(L, Conv2dDCLLlayer) and L.step_wide_supported()
+
+    def step_slab_supported(self):
+        """True if this slice's layer steps can run on k_lif_step_slab (Conv2dDCLLlayer.step_slab_supported)."""
+        L = self.dclllayer
+        return isinstance(L, Conv2dDCLLlayer) and L.step_slab_supported()
 
     def _backward_from_pv(self):
         """True if this slice's backward can take sigmoid' from pv: no pooling, <= 32 readout rows (k_bwd_dv_nopool)."""

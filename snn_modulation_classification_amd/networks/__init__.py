@@ -310,6 +310,7 @@ class ConvNetwork(torch.nn.Module):
             sig.append(bool(s.slab_learning_path))
             sig.append(bool(L.i2h.any_step_path))
             sig.append(bool(L.i2h.wide_step_path))
+            sig.append(bool(L.i2h.slab_step_path))
             sig.append((bool(s.w3_learning_path), bool(L.i2h.w3_step_path), bool(s.w3_first_wgrad), bool(s.w3_dv)))
             for t in s._adam_tensors(advance=False):
                 sig += [t['param'].data_ptr(), t['grad'].data_ptr(), t['exp_avg'].data_ptr(),
@@ -534,6 +535,7 @@ class ConvNetwork(torch.nn.Module):
             sig.append(bool(L.i2h.any_step_path))
             sig.append(bool(L.i2h.w3_step_path))
             sig.append(bool(L.i2h.wide_step_path))
+            sig.append(bool(L.i2h.slab_step_path))
         return tuple(sig)
 
     @torch.no_grad()
@@ -591,7 +593,9 @@ class ConvNetwork(torch.nn.Module):
         runs its per-step loop on k_lif_step_any).  Ignored with a notice where a layer is not served; unset or 0: nothing
         changes.  Looked at once per network, so a later `net.any_step_path = False` holds.
         DCLL_WIDE_STEP_PATH=1 = `net.wide_step_path = True` (k_lif_step_wide: layers of up to 64 output channels) by the same
-        rule; together with DCLL_ANY_STEP_PATH=1 the latter wins where it is served and this one is ignored with a notice."""
+        rule; together with DCLL_ANY_STEP_PATH=1 the latter wins where it is served and this one is ignored with a notice.
+        DCLL_SLAB_STEP_PATH=1 = `net.slab_step_path = True` (k_lif_step_slab: any number of output channels) by the same rule;
+        ignored with a notice where a layer is not served or another per-step path is already on."""
         if not (self.__dict__.get('_any_step_env_seen') or os.environ.get('DCLL_ANY_STEP_PATH', '0') in ('', '0')):
             self.__dict__['_any_step_env_seen'] = True
             if self.step_any_supported():
@@ -606,6 +610,15 @@ class ConvNetwork(torch.nn.Module):
                 print('DCLL_WIDE_STEP_PATH ignored: another per-step path (any_step_path / w3_step_path) is on')
             else:
                 self.wide_step_path = True
+        if not (self.__dict__.get('_slab_step_env_seen') or os.environ.get('DCLL_SLAB_STEP_PATH', '0') in ('', '0')):
+            self.__dict__['_slab_step_env_seen'] = True
+            if not self.step_slab_supported():
+                print('DCLL_SLAB_STEP_PATH ignored: k_lif_step_slab does not serve every layer of this network')
+            elif self.w3_step_path or any(s.dclllayer.i2h.any_step_path or s.dclllayer.i2h.wide_step_path
+                                          for s in self.dcll_slices):
+                print('DCLL_SLAB_STEP_PATH ignored: another per-step path (any_step_path / wide_step_path / w3_step_path) is on')
+            else:
+                self.slab_step_path = True
 
     def write_stats(self, writer, epoch, comment=''):
         for s in self.dcll_slices:
@@ -976,6 +989,8 @@ class ConvNetwork(torch.nn.Module):
             raise ops._lib.DCLLUnsupported('any_step_path cannot be combined with w3_step_path')
         if on and any(s.dclllayer.i2h.wide_step_path for s in self.dcll_slices):
             raise ops._lib.DCLLUnsupported('any_step_path cannot be combined with wide_step_path')
+        if on and any(s.dclllayer.i2h.slab_step_path for s in self.dcll_slices):
+            raise ops._lib.DCLLUnsupported('any_step_path cannot be combined with slab_step_path')
         if on and not self.step_any_supported():
             raise ops._lib.DCLLUnsupported('dcll_conv_lif_step_any does not serve every layer of this network')
         for s in self.dcll_slices:
@@ -1002,10 +1017,41 @@ class ConvNetwork(torch.nn.Module):
         on = bool(on)
         if on and (self.w3_step_path or any(s.dclllayer.i2h.any_step_path for s in self.dcll_slices)):
             raise ops._lib.DCLLUnsupported('wide_step_path cannot be combined with any_step_path / w3_step_path')
+        if on and any(s.dclllayer.i2h.slab_step_path for s in self.dcll_slices):
+            raise ops._lib.DCLLUnsupported('wide_step_path cannot be combined with slab_step_path')
         if on and not self.step_wide_supported():
             raise ops._lib.DCLLUnsupported('dcll_conv_lif_step_wide does not serve every layer of this network')
         for s in self.dcll_slices:
             s.dclllayer.i2h.wide_step_path = on # (part of _graph_signature and _test_signature: a capture of the other path is retaken)
+
+    # -- the MFMA per-step forward of layers of any number of output channels (k_lif_step_slab): opt-in, beside the default dispatch
+    def step_slab_supported(self):
+        """True if every layer's steps are served by dcll_conv_lif_step_slab (Conv2dDCLLlayer.step_slab_supported)."""
+        return all(s.step_slab_supported() for s in self.dcll_slices)
+
+    @property
+    def slab_step_path(self):
+        """True: every per-step layer call — net.test(x[t]), every learning timestep, Conv2dDCLLlayer.forward, the autograd
+        nodes — runs dcll_conv_lif_step_slab: k_lif_step_slab (k_lif_step_wide's chains over B x bands of rows x slabs of 64
+        output channels) for the layers of more than 64 output channels that a netscale above 2 makes and for the planes whose
+        padded eps1 image exceeds a workgroup's LDS, dcll_conv_lif_step_wide's kernels for the layers that call serves, instead
+        of dcll_conv_lif_step's dispatch.  The readout tails and the sequence calls are untouched; combines with
+        slab_learning_path, wide_learning_path, any_learning_path and the default learning path.  Default False; setting it on a
+        network that is not fully served (int8 weights, general-option layers, a plane of which not one pooled row fits), or
+        together with any_step_path, wide_step_path or w3_step_path, raises DCLLUnsupported and leaves it off; switching it off
+        is always allowed."""
+        return all(s.dclllayer.i2h.slab_step_path for s in self.dcll_slices)
+
+    @slab_step_path.setter
+    def slab_step_path(self, on):
+        on = bool(on)
+        if on and (self.w3_step_path or any(s.dclllayer.i2h.any_step_path or s.dclllayer.i2h.wide_step_path
+                                            for s in self.dcll_slices)):
+            raise ops._lib.DCLLUnsupported('slab_step_path cannot be combined with any_step_path / wide_step_path / w3_step_path')
+        if on and not self.step_slab_supported():
+            raise ops._lib.DCLLUnsupported('dcll_conv_lif_step_slab does not serve every layer of this network')
+        for s in self.dcll_slices:
+            s.dclllayer.i2h.slab_step_path = on # (part of _graph_signature and _test_signature: a capture of the other path is retaken)
 
     # -- the MFMA learning step of the (1,3) / 64-channel layers of radio_ml_conv_ref.yaml: opt-in, beside the default dispatch --
     def w3_step_supported(self):
@@ -1037,6 +1083,8 @@ class ConvNetwork(torch.nn.Module):
             raise ops._lib.DCLLUnsupported('w3_step_path cannot be combined with slab_learning_path')
         if on and any(s.dclllayer.i2h.wide_step_path for s in self.dcll_slices):
             raise ops._lib.DCLLUnsupported('w3_step_path cannot be combined with wide_step_path')
+        if on and any(s.dclllayer.i2h.slab_step_path for s in self.dcll_slices):
+            raise ops._lib.DCLLUnsupported('w3_step_path cannot be combined with slab_step_path')
         if on and not self.w3_step_supported():
             raise ops._lib.DCLLUnsupported('dcll_conv_lif_step_w3 / dcll_conv_lif_backward_w3 do not serve every layer of this '
                                            'network')

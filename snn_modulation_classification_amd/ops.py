@@ -112,7 +112,7 @@ def _check_layer_operands(desc, W, b, eps0, eps1, arp, B, tau=None, tau4=None):
 
 def conv_lif_step(desc, x, W, b, alpha, tau_m, alphas, tau_s, eps0, eps1, arp, i2o_W=None, i2o_b=None,
                   out_W=None, out_b=None, want_v=True, out=None, q8=None, stacked=None, finish=None, defer_ro=False,
-                  any_path=False, w3_path=False, wide_path=False):
+                  any_path=False, w3_path=False, wide_path=False, slab_path=False, bands=0):
     """One Conv2dDCLLlayer.forward step (dcll/pytorch_libdcll.py:599-608); state tensors are updated in place.
 
     Returns (s_pooled, p, o, pv_pooled, v) — p / o are None when the corresponding weights are None.
@@ -136,7 +136,17 @@ def conv_lif_step(desc, x, W, b, alpha, tau_m, alphas, tau_s, eps0, eps1, arp, i
     `wide_path`: the layer kernel is dcll_conv_lif_step_wide — k_lif_step_wide, k_lif_step_any's form with two 32-row M tiles, for
     a plain conv layer with up to 64 output channels (step_wide_supported); a layer with c_out <= 32 runs the `any_path`
     kernels, same bits and launch log.  fp32 weights only; combined with `q8`, `any_path` or `w3_path` it raises.
+    `slab_path`: the layer kernel is dcll_conv_lif_step_slab — k_lif_step_slab, k_lif_step_wide's chains over B x bands x slabs
+    workgroups (a band of output rows, a slab of 64 output channels each), for a plain conv layer of any number of output channels
+    and any plane height (step_slab_supported); `bands`: 0 = the plan's rule, N >= 1 = exactly N bands.  A layer `wide_path`
+    serves, with bands = 0, runs the `wide_path` kernels, same bits and launch log.  fp32 weights only; combined with `q8`,
+    `any_path`, `w3_path` or `wide_path` it raises.
     """
+    if slab_path and (q8 is not None or any_path or w3_path or wide_path):
+        raise ValueError("conv_lif_step(slab_path=True) cannot be combined with q8, any_path=True, w3_path=True or wide_path=True "
+                         "(fp32 weights, one layer kernel)")
+    if bands and not slab_path:
+        raise ValueError("conv_lif_step(bands=N) is an argument of slab_path=True")
     if wide_path and (q8 is not None or any_path or w3_path):
         raise ValueError("conv_lif_step(wide_path=True) cannot be combined with q8, any_path=True or w3_path=True (fp32 weights, "
                          "one layer kernel)")
@@ -172,17 +182,20 @@ def conv_lif_step(desc, x, W, b, alpha, tau_m, alphas, tau_s, eps0, eps1, arp, i
     v = buf('v', (B, desc.c_out, ch, cw), want_v)
     p = buf('p', (B, desc.target), i2o_W is not None)
     o = buf('o', (B, desc.target), bool(desc.output_layer))
-    scratch = buf('scratch', (2, B, desc.c_out, ch, cw), pooled and not any_path and not w3_path and not wide_path)
+    scratch = buf('scratch', (2, B, desc.c_out, ch, cw), pooled and not any_path and not w3_path and not wide_path and not slab_path)
     w_scratch = buf('w_scratch', (max(step_any_scratch(desc), 1),), True) if any_path else None       # (not served: the call refuses)
     if wide_path:
         w_scratch = buf('w_scratch', (max(step_wide_scratch(desc), 1),), True)
+    if slab_path:
+        w_scratch = buf('w_scratch', (max(step_slab_scratch(desc), 1),), True)
 
     def layer_step(d, *readout_args):
-        """the layer call of this step: dcll_conv_lif_step, dcll_conv_lif_step_any / _wide (w_scratch for scratch, no opts) or
-        dcll_conv_lif_step_w3 (neither)"""
+        """the layer call of this step: dcll_conv_lif_step, dcll_conv_lif_step_any / _wide (w_scratch for scratch, no opts),
+        dcll_conv_lif_step_slab (w_scratch and the band count) or dcll_conv_lif_step_w3 (neither)"""
         fn = ("dcll_conv_lif_step_w3" if w3_path else "dcll_conv_lif_step_any" if any_path else
-              "dcll_conv_lif_step_wide" if wide_path else "dcll_conv_lif_step")
-        tail = () if w3_path else (ptr(w_scratch),) if any_path or wide_path else (ptr(scratch), opts)
+              "dcll_conv_lif_step_wide" if wide_path else "dcll_conv_lif_step_slab" if slab_path else "dcll_conv_lif_step")
+        tail = (() if w3_path else (ptr(w_scratch),) if any_path or wide_path else (ptr(w_scratch), int(bands)) if slab_path
+                else (ptr(scratch), opts))
         rc = getattr(_lib.get(), fn)(
             ctypes.byref(d), ptr(x), ptr(W), ptr(b), ptr(alpha), ptr(tau_m), ptr(alphas), ptr(tau_s),
             ptr(eps0), ptr(eps1), ptr(arp), *readout_args, ptr(pv), ptr(v), *tail, B, stream_ptr())
@@ -257,6 +270,33 @@ def step_wide_scratch(desc):
     """Floats of dcll_conv_lif_step_wide's w_scratch (dcll_conv_lif_step_wide_scratch: 128 per MFMA step of a chain; c_out <= 32:
     step_any_scratch), 0 = not served."""
     return int(_lib.get().dcll_conv_lif_step_wide_scratch(ctypes.byref(desc)))
+
+
+def step_slab_lds(desc, B=1, bands=0):
+    """LDS bytes of the largest workgroup of dcll_conv_lif_step_slab on this layer under the plan of (B, bands) — a layer that
+    call hands to dcll_conv_lif_step_wide: step_wide_lds —, 0 = the layer is not served (dcll_conv_lif_step_slab_lds)."""
+    return int(_lib.get().dcll_conv_lif_step_slab_lds(ctypes.byref(desc), int(B), int(bands)))
+
+
+def step_slab_supported(desc, B=1, bands=0):
+    """True if conv_lif_step(slab_path=True, bands=bands) serves the layer: a plain conv with a kernel up to 16x16, any number of
+    output channels, and a band plan within the 160 KiB of LDS (whether the rule's plan fits does not depend on B)."""
+    return step_slab_lds(desc, B, bands) > 0
+
+
+def step_slab_scratch(desc):
+    """Floats of dcll_conv_lif_step_slab's w_scratch (dcll_conv_lif_step_slab_scratch: 128 per MFMA step of a chain and slab of
+    64 output channels), 0 = not served."""
+    return int(_lib.get().dcll_conv_lif_step_slab_scratch(ctypes.byref(desc)))
+
+
+def step_slab_plan(desc, B, bands=0):
+    """(bands, slabs) of dcll_conv_lif_step_slab for this layer and batch (dcll_conv_lif_step_slab_plan; (0, 0): the call is
+    dcll_conv_lif_step_wide's); a refusal raises."""
+    nb, ns = ctypes.c_int32(0), ctypes.c_int32(0)
+    check(_lib.get().dcll_conv_lif_step_slab_plan(ctypes.byref(desc), int(B), int(bands), ctypes.byref(nb), ctypes.byref(ns)),
+          "dcll_conv_lif_step_slab_plan")
+    return nb.value, ns.value
 
 
 def step_w3_lds(desc):

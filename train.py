@@ -161,6 +161,14 @@ def parse_args(argv=None):
                         'net.learn 2.395-2.413 -> 1.263-1.288 at B = 512 (1.86-1.91x), but NOT faster at B = 32: 0.440-0.441 -> '
                         '0.445-0.447 (one workgroup per sample leaves CUs idle in the layers that are not split) (DESIGN 4.2e; '
                         'profiles/r21_step_wide_timing.txt; experiments/step_wide_timing.py)')
+    p.add_argument('--slab_step_path', action='store_true',
+                   help='opt in: every per-step layer call (net.test per timestep, every learning timestep) runs through '
+                        'dcll_conv_lif_step_slab — k_lif_step_slab (k_lif_step_wide\'s chains over bands of rows x slabs of 64 output '
+                        'channels) for layers of more than 64 output channels (--netscale above 2) and for planes whose padded '
+                        'eps1 image exceeds a workgroup\'s LDS, dcll_conv_lif_step_wide\'s kernels for the layers that call serves '
+                        '— where ConvNetwork.step_slab_supported() holds; ignored with a notice elsewhere and together with '
+                        '--any_step_path / --wide_step_path / --w3_step_path; combines with --slab_learning_path.  The sequence '
+                        'paths are not affected (DESIGN 4.2g; experiments/step_slab_timing.py)')
     p.add_argument('--w3_step_path', action='store_true',
                    help='opt in (radio_ml_conv_ref.yaml: the 64-channel layers with kernel (1,3), padding (0,1), pooling (1,2)): '
                         'every per-step layer call runs k_lif_step_w3 (traces, fp32-MFMA chains and pooling in one launch) and '
@@ -250,6 +258,7 @@ def main(argv=None):
     _opt_in_any_step(net, args)
     _opt_in_w3_step(net, args)
     _opt_in_wide_step(net, args)
+    _opt_in_slab_step(net, args)
     _opt_in_wide_learning(net, args)
     _opt_in_slab_learning(net, args)
     parallel.freeze_startup_heap()          # (a full GC pass over the start-up heap costs ~100 ms inside the T-loop)
@@ -558,6 +567,20 @@ def _opt_in_wide_step(net, args):
         print('--wide_step_path ignored: k_lif_step_wide does not serve every layer of this network')
 
 
+def _opt_in_slab_step(net, args):
+    """--slab_step_path: switch the network's per-step layer calls to dcll_conv_lif_step_slab (k_lif_step_slab for layers of more
+    than 64 output channels or planes beyond a workgroup's LDS, dcll_conv_lif_step_wide's kernels below) where every layer is
+    served and no other per-step path is in effect."""
+    if not getattr(args, 'slab_step_path', False):
+        return
+    if net.any_step_path or net.w3_step_path or net.wide_step_path:
+        print('--slab_step_path ignored: another per-step path (--any_step_path / --wide_step_path / --w3_step_path) is in effect')
+    elif net.step_slab_supported():
+        net.slab_step_path = True
+    else:
+        print('--slab_step_path ignored: k_lif_step_slab does not serve every layer of this network')
+
+
 def _opt_in_w3_step(net, args):
     """--w3_step_path: switch the network's per-step layer calls and weight gradients to k_lif_step_w3 / k_bwd_wgrad_w3 where
     every layer is served; --w3_first_wgrad with it: the first layer's weight gradient on k_bwd_wgrad_w3f; --w3_dv_path with it:
@@ -610,6 +633,7 @@ def main_mnist(args):
     _opt_in_any_step(net, args)
     _opt_in_w3_step(net, args)
     _opt_in_wide_step(net, args)
+    _opt_in_slab_step(net, args)
     _opt_in_wide_learning(net, args)
     _opt_in_slab_learning(net, args)
     use_wide = _opt_in_wide_sequence(net, args, net.sequence_supported())      # (the condition of --any_sequence_path below)
