@@ -780,6 +780,47 @@ int dcll_conv_lif_backward_slab_open(const dcll_conv_desc *d, const float *eps1,
                                      const float **part, int32_t *nchunk, void *stream);
 
 /*
+ * Found by symbol lookup (DCLL_ABI_VERSION is unchanged) — the calls above for ANY plane height (k_bwd_wgrad_band,
+ * csrc/dcll_bwd_band.hip): arguments, results and scratch rule of dcll_conv_lif_backward_slab / _slab_open plus `bands`.  Additions
+ * only: the default dispatch, the _any, _wide and _slab calls, their launch logs and refusals are unchanged; dv, the fixed-order
+ * reduction and the output_ gradient are the same kernels.
+ * k_bwd_wgrad_any / _wide / _slab stage a whole sample in LDS and refuse a layer whose sample does not fit.  Here a sample is cut
+ * into NB bands of RB conv-output rows: band k covers the rows [min(ch, k RB), min(ch, (k + 1) RB)).  A job is (sample b, band k),
+ * job = b NB + k; workgroup (chunk, column split, slab) runs the jobs chunk, chunk + nchunk, ... in order, accumulates in registers
+ * and stores part[chunk][co][c_in kh kw + 1] once; nchunk = min(B NB, 256, what the scratch holds).  Per job it stages the band's
+ * rows of its slab's dv rows and the rb + kh - 1 padded input rows under them of its column tiles' channels:
+ *   4 bytes x (cg (RB + kh - 1)(w + 2 pad_w) + 1 + min(c_out, 32 MT) ((RB (cw rounded up to even)) | 1)),  MT = c_out <= 32 ? 1 : 2
+ * which does not grow with the plane height.  MT = 2: the slab rule of dcll_conv_lif_backward_slab (NS <= 65 535).
+ * bands == 0: the library's rule.  Where dcll_conv_lif_backward_slab serves the layer the call IS that call — same kernels, launch
+ *   log, bits, _lds value and refusals.  Otherwise: the largest TPW <= min(NT, 32) column tiles per workgroup at which a band of
+ *   min(ch, kh) rows fits the 160 KiB (failing that at every TPW: at which ONE row fits), the largest RB that fits beside it, NB = ceil(ch / RB),
+ *   RB = ceil(ch / NB); then the small-batch lowering of TPW over nchunk x NS workgroups, never beyond the full launch's LDS.
+ * bands == 1: the _slab call itself, refused where that call refuses.
+ * bands == N >= 2: exactly N bands of ceil(ch / N) rows (the last ones empty where (N - 1) ceil(ch / N) >= ch), TPW the largest
+ *   that fits.
+ * Refused before any launch (DCLL_ERR_UNSUPPORTED): non-plain convs, kernels beyond 16x16, bands > ch, bands < 0, a forced band that
+ * does not fit, a layer of which not even a one-row band with one column tile fits, more than 65 535 slabs or column splits;
+ * DCLL_ERR_INVALID: scratch_floats < B c_out ch cw + c_out (c_in kh kw + 1).
+ * The launch log names the form: "k_bwd_wgrad_band<MT,NQ>[ (column split)][ (pixel split)]" (both: "(column split, pixel split)"),
+ * NQ = column tiles per wave (1, 2, 4).  Every sum has a fixed order: two runs give the same bits, and _bands_open +
+ * dcll_grad_reduce_adam gives _bands' bits.  Not bit-identical to the other backward calls.
+ * dcll_conv_lif_backward_bands_lds: LDS bytes per workgroup of a full launch (no launch uses more), 0 where the layer is not served.
+ * dcll_conv_lif_backward_bands_plan: host only, launches nothing; out = NB, RB, TPW, PS (pixel split), NQ, NS (slabs), column splits,
+ * nchunk of a call with an unlimited scratch.  A call that IS the _slab call reports NB = 1, RB = ch, NS and min(B, 256) chunks,
+ * and 0 for TPW, PS, NQ and the column splits (that call's own plan).  Returns DCLL_OK or the refusal's code.
+ */
+int64_t dcll_conv_lif_backward_bands_lds(const dcll_conv_desc *d, int32_t bands);
+int dcll_conv_lif_backward_bands_plan(const dcll_conv_desc *d, int32_t B, int32_t bands, int32_t out[8]);
+int dcll_conv_lif_backward_bands(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                                 const float *g_p, const float *g_o, const float *g_pv, const float *g_v, const float *i2o_W,
+                                 float *dW, float *db, float *d_outW, float *d_outb, float *scratch, int64_t scratch_floats,
+                                 int32_t B, int32_t bands, void *stream);
+int dcll_conv_lif_backward_bands_open(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                                      const float *g_p, const float *g_o, const float *g_pv, const float *g_v, const float *i2o_W,
+                                      float *d_outW, float *d_outb, float *scratch, int64_t scratch_floats, int32_t B,
+                                      int32_t bands, const float **part, int32_t *nchunk, void *stream);
+
+/*
  * ABI 10 — one layer step of ANY plain conv layer in one MFMA launch (k_lif_step_any): dcll_conv_lif_step with the same arguments
  * and results for the layers that call serves with k_trace + k_conv_lif[_tiled] + k_pool.  Additions only: dcll_conv_lif_step, its
  * dispatch, launch logs and refusals are unchanged.  Differences to dcll_conv_lif_step:

@@ -170,6 +170,10 @@ SIGNATURES = {
     "dcll_conv_lif_backward_slab_lds": (_I64, [_DP]),
     "dcll_conv_lif_backward_slab": (_I32, [_DP] + [_P] * 13 + [_I64, _I32, _P]),
     "dcll_conv_lif_backward_slab_open": (_I32, [_DP] + [_P] * 11 + [_I64, _I32, ctypes.POINTER(ctypes.c_void_p), _IP, _P]),
+    "dcll_conv_lif_backward_bands_lds": (_I64, [_DP, _I32]),
+    "dcll_conv_lif_backward_bands_plan": (_I32, [_DP, _I32, _I32, _IP]),
+    "dcll_conv_lif_backward_bands": (_I32, [_DP] + [_P] * 13 + [_I64, _I32, _I32, _P]),
+    "dcll_conv_lif_backward_bands_open": (_I32, [_DP] + [_P] * 11 + [_I64, _I32, _I32, ctypes.POINTER(ctypes.c_void_p), _IP, _P]),
     "dcll_conv_lif_step_any_lds": (_I64, [_DP]),
     "dcll_conv_lif_step_any_scratch": (_I64, [_DP]),
     "dcll_conv_lif_step_any": (_I32, [_DP] + [_P] * 20 + [_I32, _P]),

@@ -3672,7 +3672,7 @@ __global__ __launch_bounds__(256) void k_bwd_outgrad_mfma(const float *__restric
 }
 
 // the weight-gradient kernel of a backward call: the default dispatch, or one of the opt-in entry points' kernels
-enum wgrad_sel { WGRAD_DEFAULT, WGRAD_ANY, WGRAD_W3, WGRAD_W3F, WGRAD_WIDE, WGRAD_SLAB };
+enum wgrad_sel { WGRAD_DEFAULT, WGRAD_ANY, WGRAD_W3, WGRAD_W3F, WGRAD_WIDE, WGRAD_SLAB, WGRAD_BAND };
 
 // open_part != nullptr: the weight gradient's partial rows are left in scratch (*open_part, *open_nchunk) for
 // dcll_grad_reduce_adam; dW / db are not written
@@ -3681,7 +3681,7 @@ static int conv_lif_backward_impl(const dcll_conv_desc *d, const float *eps1, co
                                   const float *i2o_W, float *dW, float *db, float *d_outW, float *d_outb,
                                   float *scratch, int64_t scratch_floats, int32_t B, void *stream,
                                   const float **open_part, int32_t *open_nchunk, bool dv_done = false,
-                                  wgrad_sel sel = WGRAD_DEFAULT, bool dv_w3 = false)
+                                  wgrad_sel sel = WGRAD_DEFAULT, bool dv_w3 = false, int32_t bands = 0)
 {
     // WGRAD_ANY: the weight gradient by k_bwd_wgrad_any (dcll_bwd_any.hip) whatever the geometry — none of the specialised
     // kernels, and neither the tap nor the row-width limit of the generic k_bwd_wgrad.  WGRAD_W3: by k_bwd_wgrad_w3
@@ -3691,8 +3691,12 @@ static int conv_lif_backward_impl(const dcll_conv_desc *d, const float *eps1, co
     // WGRAD_ANY (dcll_conv_lif_backward_wide hands narrower layers to WGRAD_ANY before it gets here)
     // WGRAD_SLAB: by k_bwd_wgrad_slab (dcll_bwd_slab.hip) for the layers of more than 64 output channels, in slabs of 64, without the
     // tap limit (dcll_conv_lif_backward_slab hands narrower layers to WGRAD_WIDE / WGRAD_ANY before it gets here)
+    // WGRAD_BAND: by k_bwd_wgrad_band (dcll_bwd_band.hip) in bands of conv-output rows (`bands`: 0 the rule, N >= 2 forced), for the
+    // planes whose sample the three kernels above cannot stage (dcll_conv_lif_backward_bands hands the layers and band counts
+    // that dcll_conv_lif_backward_slab serves to the selectors above before it gets here)
     // dv_w3 (with WGRAD_W3 / WGRAD_W3F only): the dv plane by k_bwd_dv_w3 (dcll_step_w3.hip) instead of k_bwd_dv, same bits
     const bool any = sel == WGRAD_ANY, wide = sel == WGRAD_WIDE, slab = sel == WGRAD_SLAB, w3f = sel == WGRAD_W3F, w3 = sel == WGRAD_W3 || w3f;
+    const bool band = sel == WGRAD_BAND;
     int rc = check_desc(d);
     if (rc) return rc;
     const bool nopool = d->pool_h == 1 && d->pool_w == 1 && d->target <= 32;
@@ -3701,7 +3705,7 @@ static int conv_lif_backward_impl(const dcll_conv_desc *d, const float *eps1, co
         return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward: v may be NULL only for a layer without pooling whose pv is given");
     if (g_p && !i2o_W) return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward: g_p needs i2o_W");
     if (g_o && (!pv_pooled || !d_outW || !d_outb)) return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward: g_o needs pv_pooled, d_outW, d_outb");
-    if (!any && !wide && !slab && d->kh * d->kw > WG_MAXTAPS) return fail(DCLL_ERR_UNSUPPORTED, "dcll_conv_lif_backward: kernels up to 64 taps (kh * kw <= 64)");
+    if (!any && !wide && !slab && !band && d->kh * d->kw > WG_MAXTAPS) return fail(DCLL_ERR_UNSUPPORTED, "dcll_conv_lif_backward: kernels up to 64 taps (kh * kw <= 64)");
     if (B < 1) return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward: empty batch");
     hipStream_t st = (hipStream_t)stream;
     int ch, cw, ph, pw;
@@ -3721,6 +3725,11 @@ static int conv_lif_backward_impl(const dcll_conv_desc *d, const float *eps1, co
         if ((rc = dcll_bwd_wgrad_slab_check(d, "dcll_conv_lif_backward_slab")) != DCLL_OK) return rc;
         if (scratch_floats < nconv + (long)d->c_out * ((long)d->c_in * d->kh * d->kw + 1))
             return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward_slab: scratch too small (need B*c_out*ch*cw + k*(c_out*(c_in*kh*kw+1)), k >= 1)");
+    }
+    if (band) {     // likewise
+        if ((rc = dcll_bwd_wgrad_band_check(d, bands, "dcll_conv_lif_backward_bands")) != DCLL_OK) return rc;
+        if (scratch_floats < nconv + (long)d->c_out * ((long)d->c_in * d->kh * d->kw + 1))
+            return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward_bands: scratch too small (need B*c_out*ch*cw + k*(c_out*(c_in*kh*kw+1)), k >= 1)");
     }
     if (w3) {       // likewise
         if ((rc = dcll_bwd_w3_check(d, "dcll_conv_lif_backward_w3")) != DCLL_OK) return rc;
@@ -3776,6 +3785,8 @@ static int conv_lif_backward_impl(const dcll_conv_desc *d, const float *eps1, co
         if ((rc = dcll_launch_bwd_wgrad_wide(d, scratch, eps1, part, B, &nchunk, st)) != DCLL_OK) return rc;
     } else if (slab) {
         if ((rc = dcll_launch_bwd_wgrad_slab(d, scratch, eps1, part, B, &nchunk, st)) != DCLL_OK) return rc;
+    } else if (band) {
+        if ((rc = dcll_launch_bwd_wgrad_band(d, bands, scratch, eps1, part, B, &nchunk, st)) != DCLL_OK) return rc;
     } else if (w3 && d->c_in == 64) {
         if ((rc = dcll_launch_bwd_wgrad_w3(d, scratch, eps1, part, B, &nchunk, st, true)) != DCLL_OK) return rc;
     } else if (w3f && d->c_in == 1) {
@@ -3965,6 +3976,32 @@ extern "C" int dcll_conv_lif_backward_slab_open(const dcll_conv_desc *d, const f
     if (!part || !nchunk) return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward_slab_open: null part / nchunk");
     return conv_lif_backward_impl(d, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, nullptr, nullptr, d_outW, d_outb, scratch,
                                   scratch_floats, B, stream, part, nchunk, false, slab_sel(d));
+}
+
+// found by symbol lookup (the ABI version stays 10): the same two calls with the weight gradient on k_bwd_wgrad_band
+// (dcll_bwd_band.hip; dcll_conv_lif_backward_bands_lds is the predicate), a sample cut into bands of conv-output rows: any plane
+// height.  bands == 1, and bands == 0 on a layer dcll_conv_lif_backward_slab serves: the _slab call itself — same kernels, launch
+// log, bits and refusals
+static wgrad_sel band_sel(const dcll_conv_desc *d, int32_t bands) { return dcll_bwd_band_forwards(d, bands) ? slab_sel(d) : WGRAD_BAND; }
+
+extern "C" int dcll_conv_lif_backward_bands(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                                            const float *g_p, const float *g_o, const float *g_pv, const float *g_v,
+                                            const float *i2o_W, float *dW, float *db, float *d_outW, float *d_outb,
+                                            float *scratch, int64_t scratch_floats, int32_t B, int32_t bands, void *stream)
+{
+    return conv_lif_backward_impl(d, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, dW, db, d_outW, d_outb, scratch,
+                                  scratch_floats, B, stream, nullptr, nullptr, false, band_sel(d, bands), false, bands);
+}
+
+extern "C" int dcll_conv_lif_backward_bands_open(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                                                 const float *g_p, const float *g_o, const float *g_pv, const float *g_v,
+                                                 const float *i2o_W, float *d_outW, float *d_outb, float *scratch,
+                                                 int64_t scratch_floats, int32_t B, int32_t bands, const float **part,
+                                                 int32_t *nchunk, void *stream)
+{
+    if (!part || !nchunk) return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward_bands_open: null part / nchunk");
+    return conv_lif_backward_impl(d, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, nullptr, nullptr, d_outW, d_outb, scratch,
+                                  scratch_floats, B, stream, part, nchunk, false, band_sel(d, bands), false, bands);
 }
 
 // added under ABI 10: the same two calls with the weight gradient of a 64 -> 64 layer of the (1,3) / (1,2)-pool geometry on

@@ -204,6 +204,15 @@ int dcll_launch_step_wide(const dcll_conv_desc *d, const float *x, const float *
                           const float *tau_m, const float *alphas, const float *tau_s, float *eps0, float *eps1, float *arp,
                           float *out_s, float *out_pv, float *out_v, int ns, int32_t B, hipStream_t st, bool launch);
 
+// k_bwd_wgrad_band (dcll_bwd_band.hip): the same for a plain conv layer of any c_out on any plane height, a sample in bands of
+// conv-output rows (bands: 0 the rule, N >= 2 forced).  _forwards: the call is dcll_conv_lif_backward_slab's (bands == 1, or
+// bands == 0 on a layer that call serves) and never reaches the rest; _check and launcher as for k_bwd_wgrad_slab
+__attribute__((visibility("hidden"))) bool dcll_bwd_band_forwards(const dcll_conv_desc *d, int32_t bands);
+__attribute__((visibility("hidden"))) int dcll_bwd_wgrad_band_check(const dcll_conv_desc *d, int32_t bands, const char *who);
+__attribute__((visibility("hidden")))
+int dcll_launch_bwd_wgrad_band(const dcll_conv_desc *d, int32_t bands, const float *gvf, const float *eps1, float *part, int32_t B,
+                               long *nchunk, hipStream_t st);
+
 // k_lif_step_slab (dcll_step_slab.hip): one MFMA layer step of a plain conv layer of any number of output channels (kernel up to
 // 16x16) in bands of rows and slabs of 64 channels.  _forwards: the call is dcll_conv_lif_step_wide's (c_out <= 64, bands == 0,
 // served there) and never reaches the rest; _plan: DCLL_OK with the bands and slabs of a call (bands == 0: the rule) or the

@@ -1225,6 +1225,9 @@ class DCLLBase(nn.Module):
 
     slab_learning_path = False      # _learn_tail: dcll_conv_lif_backward_slab[_open] (k_bwd_wgrad_slab: layers of any width, 64-channel slabs)
 
+    band_learning_path = False      # _learn_tail: dcll_conv_lif_backward_bands[_open] (k_bwd_wgrad_band: any plane height, a sample in bands
+                                    # of conv rows); True: the library's band rule, an int N: that many bands
+
     w3_learning_path = False        # _learn_tail: dcll_conv_lif_backward_w3[_open] (k_bwd_wgrad_w3); set by ConvNetwork.w3_step_path
     w3_first_wgrad = False          # with w3_learning_path: dcll_conv_lif_backward_w3f[_open] (the c_in 1 layer on k_bwd_wgrad_w3f);
                                     # set by ConvNetwork.w3_first_wgrad
@@ -1263,6 +1266,19 @@ class DCLLBase(nn.Module):
             return False
         return ops.backward_slab_supported(L.i2h.make_desc(L.im_dims, L.pooling, L.i2o.weight.shape[0], L.output_layer))
 
+    def _band_count(self):
+        """The `bands` argument band_learning_path stands for: True -> 0 (the library's rule), an int N -> N."""
+        v = self.band_learning_path
+        return 0 if v is True or v is False else int(v)
+
+    def backward_bands_supported(self, bands=0):
+        """True if this slice's native learning step can take its weight gradient from dcll_conv_lif_backward_bands with that band
+        count (0: the library's rule): as backward_slab_supported on a plane of any height (ops.backward_bands_supported)."""
+        L = self.dclllayer
+        if not isinstance(L, Conv2dDCLLlayer) or L.i2h._general():
+            return False
+        return ops.backward_bands_supported(L.i2h.make_desc(L.im_dims, L.pooling, L.i2o.weight.shape[0], L.output_layer), bands)
+
     def step_any_supported(self):
         """True if this slice's layer steps can run on k_lif_step_any (Conv2dDCLLlayer.step_any_supported)."""
         L = self.dclllayer
@@ -1289,7 +1305,7 @@ class DCLLBase(nn.Module):
         dcll_conv_lif_backward into the parameters' .grad.  `open_reduce`: the weight gradient's last reduction is left to
         the caller's ops.grad_reduce_adam (self._learn_bufs['grads']['parts']); `defer_backward` (a list, with open_reduce): the
         backward is not launched here but appended for ops.conv_lif_backward_open_multi (all slices' dv in one launch) — with
-        any_learning_path, wide_learning_path, slab_learning_path or w3_learning_path the slice's own open call is launched at once instead.
+        any_learning_path, wide_learning_path, slab_learning_path, band_learning_path or w3_learning_path the slice's own open call is launched at once instead.
         -> loss (1,) device tensor or None"""
         L = self.dclllayer
         i2h = L.i2h
@@ -1324,7 +1340,8 @@ class DCLLBase(nn.Module):
                                   want_out=L.output_layer, out=gb, open_reduce=open_reduce,
                                   defer=defer_backward if open_reduce else None, any_path=self.any_learning_path,
                                   w3_path=self.w3_learning_path, w3_first=self.w3_first_wgrad, w3_dv=self.w3_dv,
-                                  wide_path=self.wide_learning_path, slab_path=self.slab_learning_path)
+                                  wide_path=self.wide_learning_path, slab_path=self.slab_learning_path,
+                                  band_path=self.band_learning_path is not False, bands=self._band_count())
         return loss
 
     def _grads_into_slab(self):

@@ -308,6 +308,7 @@ class ConvNetwork(torch.nn.Module):
             sig.append(bool(s.any_learning_path))
             sig.append(bool(s.wide_learning_path))
             sig.append(bool(s.slab_learning_path))
+            sig.append((s.band_learning_path is not False, s._band_count()))
             sig.append(bool(L.i2h.any_step_path))
             sig.append(bool(L.i2h.wide_step_path))
             sig.append(bool(L.i2h.slab_step_path))
@@ -911,6 +912,8 @@ class ConvNetwork(torch.nn.Module):
             raise ops._lib.DCLLUnsupported('any_learning_path cannot be combined with wide_learning_path')
         if on and any(s.slab_learning_path for s in self.dcll_slices):
             raise ops._lib.DCLLUnsupported('any_learning_path cannot be combined with slab_learning_path')
+        if on and any(s.band_learning_path is not False for s in self.dcll_slices):
+            raise ops._lib.DCLLUnsupported('any_learning_path cannot be combined with band_learning_path')
         if on and not self.backward_any_supported():
             raise ops._lib.DCLLUnsupported('dcll_conv_lif_backward_any does not serve every layer of this network')
         for s in self.dcll_slices:
@@ -937,6 +940,8 @@ class ConvNetwork(torch.nn.Module):
             raise ops._lib.DCLLUnsupported('wide_learning_path cannot be combined with w3_step_path / any_learning_path')
         if on and any(s.slab_learning_path for s in self.dcll_slices):
             raise ops._lib.DCLLUnsupported('wide_learning_path cannot be combined with slab_learning_path')
+        if on and any(s.band_learning_path is not False for s in self.dcll_slices):
+            raise ops._lib.DCLLUnsupported('wide_learning_path cannot be combined with band_learning_path')
         if on and not self.backward_wide_supported():
             raise ops._lib.DCLLUnsupported('dcll_conv_lif_backward_wide does not serve every layer of this network')
         for s in self.dcll_slices:
@@ -963,10 +968,50 @@ class ConvNetwork(torch.nn.Module):
         if on and (self.w3_step_path or any(s.any_learning_path or s.wide_learning_path or s.w3_learning_path for s in self.dcll_slices)):
             raise ops._lib.DCLLUnsupported('slab_learning_path cannot be combined with w3_step_path / any_learning_path / '
                                            'wide_learning_path')
+        if on and any(s.band_learning_path is not False for s in self.dcll_slices):
+            raise ops._lib.DCLLUnsupported('slab_learning_path cannot be combined with band_learning_path')
         if on and not self.backward_slab_supported():
             raise ops._lib.DCLLUnsupported('dcll_conv_lif_backward_slab does not serve every layer of this network')
         for s in self.dcll_slices:
             s.slab_learning_path = on           # (part of _graph_signature: a captured timestep of the other path is retaken)
+
+    # -- the MFMA weight gradient on planes of ANY height, a sample in bands of conv rows (k_bwd_wgrad_band): opt-in, beside the others --
+    def backward_bands_supported(self, bands=0):
+        """True if every slice is served by dcll_conv_lif_backward_bands with that band count (0: the library's rule;
+        DCLLBase.backward_bands_supported)."""
+        return all(s.backward_bands_supported(bands) for s in self.dcll_slices)
+
+    @property
+    def band_learning_path(self):
+        """False, True or an int N.  True: every slice's learning step takes its weight gradient from dcll_conv_lif_backward_bands —
+        k_bwd_wgrad_band (fp32 MFMA, a sample cut into bands of conv-output rows: LDS does not grow with the plane height) for the
+        layers whose sample the slab path cannot stage, dcll_conv_lif_backward_slab's kernels for the layers that call serves —
+        instead of the default dispatch.  An int N >= 2: exactly N bands per sample in every slice (1: the slab call itself).  The
+        step's structure is unchanged: layer kernels, tails, one dcll_grad_reduce_adam.  Default False; setting it on a network with
+        a slice that is not served, or together with w3_step_path, any_learning_path, wide_learning_path or slab_learning_path,
+        raises DCLLUnsupported and leaves it off; switching it off is always allowed.  Combines with any_step_path, wide_step_path
+        and slab_step_path."""
+        vals = [s.band_learning_path for s in self.dcll_slices]
+        return vals[0] if vals and all(v is not False and v == vals[0] and type(v) is type(vals[0]) for v in vals) else False
+
+    @band_learning_path.setter
+    def band_learning_path(self, on):
+        if on is None or on is False:
+            on = False
+        elif on is not True:
+            on = int(on)
+            if on < 0:
+                raise ops._lib.DCLLUnsupported('band_learning_path: a band count is >= 0')
+            if on == 0:
+                on = True                       # (0 bands: the library's rule)
+        if on is not False and (self.w3_step_path or any(s.any_learning_path or s.wide_learning_path or s.slab_learning_path or
+                                                         s.w3_learning_path for s in self.dcll_slices)):
+            raise ops._lib.DCLLUnsupported('band_learning_path cannot be combined with w3_step_path / any_learning_path / '
+                                           'wide_learning_path / slab_learning_path')
+        if on is not False and not self.backward_bands_supported(0 if on is True else on):
+            raise ops._lib.DCLLUnsupported('dcll_conv_lif_backward_bands does not serve every layer of this network')
+        for s in self.dcll_slices:
+            s.band_learning_path = on           # (part of _graph_signature: a captured timestep of the other path is retaken)
 
     # -- the MFMA per-step forward of any plain conv layer (k_lif_step_any, ABI 10): opt-in, beside the default dispatch -------
     def step_any_supported(self):
@@ -1081,6 +1126,8 @@ class ConvNetwork(torch.nn.Module):
             raise ops._lib.DCLLUnsupported('w3_step_path cannot be combined with wide_learning_path')
         if on and any(s.slab_learning_path for s in self.dcll_slices):
             raise ops._lib.DCLLUnsupported('w3_step_path cannot be combined with slab_learning_path')
+        if on and any(s.band_learning_path is not False for s in self.dcll_slices):
+            raise ops._lib.DCLLUnsupported('w3_step_path cannot be combined with band_learning_path')
         if on and any(s.dclllayer.i2h.wide_step_path for s in self.dcll_slices):
             raise ops._lib.DCLLUnsupported('w3_step_path cannot be combined with wide_step_path')
         if on and any(s.dclllayer.i2h.slab_step_path for s in self.dcll_slices):

@@ -357,13 +357,36 @@ def backward_slab_supported(desc):
     return backward_slab_lds(desc) > 0
 
 
+def backward_bands_lds(desc, bands=0):
+    """LDS bytes per workgroup of a full launch of conv_lif_backward(band_path=True, bands=bands) on this layer (k_bwd_wgrad_band; a
+    call that is the slab path's: backward_slab_lds), 0 = not served (dcll_conv_lif_backward_bands_lds)."""
+    return int(_lib.get().dcll_conv_lif_backward_bands_lds(ctypes.byref(desc), int(bands)))
+
+
+def backward_bands_supported(desc, bands=0):
+    """True if conv_lif_backward(band_path=True, bands=bands) serves the layer: a plain conv of any c_out on a plane of any height, a
+    kernel up to 16x16; bands == 0 (the library's rule): a one-row band with one column tile fits the 160 KiB of LDS; bands == 1:
+    backward_slab_supported; bands == N >= 2: N <= ch and a band of ceil(ch / N) rows fits."""
+    return backward_bands_lds(desc, bands) > 0
+
+
+def backward_bands_plan(desc, B, bands=0):
+    """The launch plan of conv_lif_backward(band_path=True, bands=bands) on a batch of B with an unlimited scratch
+    (dcll_conv_lif_backward_bands_plan; nothing is launched) -> dict(NB, RB, TPW, PS, NQ, NS, nsplit, nchunk).  A call that is the
+    slab path's own reports NB = 1, RB = ch and 0 for TPW, PS, NQ, nsplit.  A layer that is not served raises."""
+    out = (ctypes.c_int32 * 8)()
+    check(_lib.get().dcll_conv_lif_backward_bands_plan(ctypes.byref(desc), int(B), int(bands), out), "dcll_conv_lif_backward_bands_plan")
+    return dict(zip(("NB", "RB", "TPW", "PS", "NQ", "NS", "nsplit", "nchunk"), (int(v) for v in out)))
+
+
 BWD_ANY_MAX_CHUNKS = 256        # batch chunks (partial rows) of k_bwd_wgrad_any, at most
 BWD_W3F_PB = 128                # pixels of a job of k_bwd_wgrad_w3f (the flattened B x h w stream): at most one partial row per job
 W3_FIRST_WGRAD, W3_DV = 1, 2    # flag bits of dcll_conv_lif_backward_w3_ex[_open] (DCLL_W3_FIRST_WGRAD, DCLL_W3_DV)
 
 
 def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want_out, out=None, open_reduce=False, defer=None,
-                      any_path=False, w3_path=False, w3_first=False, w3_dv=False, wide_path=False, slab_path=False):
+                      any_path=False, w3_path=False, w3_first=False, w3_dv=False, wide_path=False, slab_path=False,
+                      band_path=False, bands=0):
     """Gradients of one layer step (dcll_conv_lif_backward) -> (dW, db, d_outW, d_outb).  `out`: optional dict with
     preallocated 'dW', 'db', 'd_outW', 'd_outb', 'bwd_scratch' (the learning loop writes into the parameters' .grad).
     `open_reduce`: dcll_conv_lif_backward_open — dW / db are NOT written yet; the partial rows of the weight gradient stay
@@ -384,7 +407,16 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
     same bits and launch log.  `defer` as for `any_path`; combined with `any_path` or `w3_path` it raises.
     `slab_path`: dcll_conv_lif_backward_slab[_open] — the weight gradient of a plain conv layer of ANY width on k_bwd_wgrad_slab (fp32
     MFMA, one slab of 64 output channels per workgroup; backward_slab_supported); a layer with c_out <= 64 runs the `wide_path`
-    kernels, same bits and launch log.  `defer` as for `any_path`; combined with any other path it raises."""
+    kernels, same bits and launch log.  `defer` as for `any_path`; combined with any other path it raises.
+    `band_path`: dcll_conv_lif_backward_bands[_open] — the weight gradient of a plain conv layer of any width on a plane of ANY height
+    on k_bwd_wgrad_band (fp32 MFMA, a sample in bands of conv-output rows; backward_bands_supported).  `bands` (with `band_path`;
+    alone it raises): 0 the library's rule — a layer the `slab_path` serves runs that path, same bits and launch log —, 1 the
+    `slab_path` call itself, N >= 2 exactly N bands.  The partial-row scratch is sized from backward_bands_plan's nchunk.  `defer` as
+    for `any_path`; combined with any other path it raises."""
+    if band_path and (any_path or w3_path or wide_path or slab_path):
+        raise ValueError("conv_lif_backward(band_path=True) cannot be combined with any_path=True, w3_path=True, wide_path=True or slab_path=True")
+    if bands and not band_path:
+        raise ValueError("conv_lif_backward(bands=N) needs band_path=True")
     if slab_path and (any_path or w3_path or wide_path):
         raise ValueError("conv_lif_backward(slab_path=True) cannot be combined with any_path=True, w3_path=True or wide_path=True")
     if wide_path and (any_path or w3_path):
@@ -420,6 +452,8 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
     nchunk = min(jobs, 1024 if desc.c_in == 1 else 256)      # (first layer: 128-thread workgroups, 6 KB partial rows)
     if any_path or wide_path or slab_path:
         nchunk = min(B, BWD_ANY_MAX_CHUNKS)
+    if band_path:       # (a refused layer: one row, the call itself then raises with the library's message)
+        nchunk = backward_bands_plan(desc, B, bands)["nchunk"] if backward_bands_supported(desc, bands) else 1
     if w3_path and desc.c_in == 64:
         nchunk = min(-(-B * desc.h * desc.w // 128), BWD_ANY_MAX_CHUNKS)       # (k_bwd_wgrad_w3: one row per 128-pixel block)
     if w3_first and desc.c_in == 1:
@@ -443,10 +477,13 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
         fn = "dcll_conv_lif_backward_wide"
     if slab_path:
         fn = "dcll_conv_lif_backward_slab"
+    if band_path:
+        fn = "dcll_conv_lif_backward_bands"
+    band_arg = (int(bands),) if band_path else ()
     flags = ()
     if w3_dv:       # (the flag-word entry points; without w3_dv the calls above are made as before)
         fn, flags = "dcll_conv_lif_backward_w3_ex", (W3_DV | (W3_FIRST_WGRAD if w3_first else 0),)
-    if defer is not None and not any_path and not w3_path and not wide_path and not slab_path:       # (open form, launched later with other layers': conv_lif_backward_open_multi)
+    if defer is not None and not any_path and not w3_path and not wide_path and not slab_path and not band_path:       # (open form, launched later with other layers': conv_lif_backward_open_multi)
         item = _lib.BwdItem(ctypes.pointer(desc), ptr(eps1), ptr(v), ptr(pv_pooled), ptr(gp_), ptr(go_), ptr(gpv_), ptr(gv_),
                             ptr(i2o_W), ptr(d_outW), ptr(d_outb), ptr(scratch), n_scratch, B, 0, None, 0, 0)
         defer.append(dict(item=item, out=out, desc=desc, dW=dW, db=db, scratch=scratch,
@@ -456,7 +493,7 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
         part, nchunk = ctypes.c_void_p(), ctypes.c_int32()
         rc = getattr(_lib.get(), fn + "_open")(
             ctypes.byref(desc), ptr(eps1), ptr(v), ptr(pv_pooled), ptr(gp_), ptr(go_),
-            ptr(gpv_), ptr(gv_), ptr(i2o_W), ptr(d_outW), ptr(d_outb), ptr(scratch), n_scratch, B,
+            ptr(gpv_), ptr(gv_), ptr(i2o_W), ptr(d_outW), ptr(d_outb), ptr(scratch), n_scratch, B, *band_arg,
             ctypes.byref(part), ctypes.byref(nchunk), *flags, stream_ptr())
         check(rc, fn + "_open")
         out['parts'] = dict(part=part.value, nchunk=nchunk.value, c_out=desc.c_out,
@@ -465,7 +502,7 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
     rc = getattr(_lib.get(), fn)(
         ctypes.byref(desc), ptr(eps1), ptr(v), ptr(pv_pooled), ptr(gp_), ptr(go_),
         ptr(gpv_), ptr(gv_), ptr(i2o_W), ptr(dW), ptr(db), ptr(d_outW), ptr(d_outb), ptr(scratch), n_scratch, B,
-        *flags, stream_ptr())
+        *band_arg, *flags, stream_ptr())
     check(rc, fn)
     return dW, db, d_outW, d_outb
 

@@ -142,6 +142,20 @@ def parse_args(argv=None):
                         'ConvNetwork.backward_slab_supported() holds; ignored with a notice elsewhere and together with '
                         '--any_learning_path / --wide_learning_path / --w3_step_path.  Measured on an MI355X against the same tree without the flag, five alternating fresh processes, min-max ms per net.learn timestep, radio_ml_conv.yaml on 16x16, T = 128: netscale 3: 15.55-15.57 -> 1.552-1.563 at B = 64 (9.9-10.0x), 42.04-42.09 -> 9.245-9.313 at B = 512 (4.5x); netscale 4: 27.45-27.49 -> 2.332-2.356 at B = 64 (11.7-11.8x), 74.35-74.56 -> 14.78-14.90 at B = 512 (5.0x); every layer\'s open backward call is faster, none slower; the votes of the free-running arms are NOT equal (another summation order under Adam); the forward of such layers stays on the default kernels (DESIGN 4.2f; '
                         'experiments/slab_timing.py)')
+    p.add_argument('--band_learning_path', nargs='?', type=int, const=0, default=None, metavar='N',
+                   help='opt in: every layer\'s weight gradient of the learning step runs through dcll_conv_lif_backward_bands — '
+                        'k_bwd_wgrad_band (fp32 MFMA, a sample cut into bands of conv-output rows, so LDS does not grow with the '
+                        'plane height) for the layers whose sample --slab_learning_path cannot stage (netscale 2 on 24x40, 48x48 and '
+                        'larger planes, kernels above 64 taps there), that path\'s kernels for the layers it serves — where '
+                        'ConvNetwork.backward_bands_supported() holds.  N: exactly N bands per sample (default: the library\'s rule).  '
+                        'Ignored with a notice elsewhere and together with --any_learning_path / --wide_learning_path / '
+                        '--slab_learning_path / --w3_step_path; combines with the per-step forward paths.  Measured on an MI355X against '
+                        'the same tree without the flag, five alternating fresh processes, min-max ms per net.learn timestep, '
+                        'radio_ml_conv.yaml: netscale 2 on 24x40 (--slab_step_path in both arms) 9.788-9.810 -> 1.745-1.756 at B = 64 '
+                        '(5.6x), 52.08-52.24 -> 11.11-11.22 at B = 512 (4.6-4.7x); netscale 2 on 128x128 41.69-41.81 -> 9.60-9.75 at '
+                        'B = 16 (4.3-4.4x); NOT faster at netscale 1 on 48x48, B = 64: 1.215-1.237 -> 1.369-1.398 (the default dispatch '
+                        'there is the tiled MFMA kernel of the headline network) (DESIGN 4.2h; profiles/r27_bwd_band_timing.txt; '
+                        'experiments/bwd_band_timing.py)')
     p.add_argument('--any_step_path', action='store_true',
                    help='opt in: every per-step layer call (net.test per timestep, every learning timestep) runs k_lif_step_any '
                         '(one fp32-MFMA launch with the traces and the pooling fused in; any plain conv layer with c_out <= 32 and '
@@ -261,6 +275,7 @@ def main(argv=None):
     _opt_in_slab_step(net, args)
     _opt_in_wide_learning(net, args)
     _opt_in_slab_learning(net, args)
+    _opt_in_band_learning(net, args)
     parallel.freeze_startup_heap()          # (a full GC pass over the start-up heap costs ~100 ms inside the T-loop)
 
     if not args.no_save:
@@ -544,6 +559,25 @@ def _opt_in_slab_learning(net, args):
         print('--slab_learning_path ignored: dcll_conv_lif_backward_slab does not serve every layer of this network')
 
 
+def _opt_in_band_learning(net, args):
+    """--band_learning_path [N]: switch the network's learning step to dcll_conv_lif_backward_bands (k_bwd_wgrad_band where a sample
+    does not fit a workgroup's LDS, the slab path's kernels where it does) where every slice is served and no other learning path
+    is in effect."""
+    n = getattr(args, 'band_learning_path', None)
+    if n is None:
+        return
+    if net.any_learning_path or net.wide_learning_path or net.slab_learning_path or net.w3_step_path:
+        print('--band_learning_path ignored: another learning path (--any_learning_path / --wide_learning_path / '
+              '--slab_learning_path / --w3_step_path) is in effect')
+    elif n < 0:
+        print('--band_learning_path ignored: a band count is >= 0')
+    elif net.backward_bands_supported(n):
+        net.band_learning_path = n if n else True
+    else:
+        print('--band_learning_path ignored: dcll_conv_lif_backward_bands does not serve every layer of this network' +
+              (' with %d bands' % n if n else ''))
+
+
 def _opt_in_any_step(net, args):
     """--any_step_path: switch the network's per-step layer calls to k_lif_step_any where every layer is served."""
     if not args.any_step_path:
@@ -636,6 +670,7 @@ def main_mnist(args):
     _opt_in_slab_step(net, args)
     _opt_in_wide_learning(net, args)
     _opt_in_slab_learning(net, args)
+    _opt_in_band_learning(net, args)
     use_wide = _opt_in_wide_sequence(net, args, net.sequence_supported())      # (the condition of --any_sequence_path below)
     use_bands = _opt_in_band_sequence(net, args, net.sequence_supported())
     use_tiles = _opt_in_tile_sequence(net, args, net.sequence_supported())
