@@ -1046,6 +1046,47 @@ int dcll_conv_lif_backward_w3_ex_open(const dcll_conv_desc *d, const float *eps1
                                       float *d_outW, float *d_outb, float *scratch, int64_t scratch_floats, int32_t B,
                                       const float **part, int32_t *nchunk, uint32_t flags, void *stream);
 
+/*
+ * Found by symbol lookup as well (DCLL_ABI_VERSION stays 10) — the backward calls behind one pair of entry points, with a flag
+ * word.  path names the call: DCLL_BWD_DEFAULT dcll_conv_lif_backward[_open], DCLL_BWD_ANY / _WIDE / _SLAB / _BANDS the call of that
+ * suffix; bands is the argument of dcll_conv_lif_backward_bands and must be 0 with every other path.  flags == 0 IS the named
+ * call: its bits, its launch log, its refusals and its scratch rule.
+ * DCLL_BWD_POOL_DV: the "k_bwd_dv" launch of that call is replaced by k_bwd_dv_pool (csrc/dcll_bwd_dv_pool.hip) where
+ * dcll_bwd_dv_pool_served(d, B) == 1 — a streaming form of the same formula for a layer that pools: a thread owns one pooled
+ * window (k = (co, py, px), consecutive threads consecutive k) with its readout weights in registers over a chunk of samples (8, or 4 / 2
+ * where 8 would leave fewer than 512 workgroups),
+ * takes the sigmoid of each of the window's in-range elements once, picks the first maximum in row-major order (strict > on the
+ * sigmoids) and writes the window; the trailing rows / columns that belong to no window (an odd plane under pool 2, the last row /
+ * column of a plane divisible by 3 under pool 3) are written by the threads of the last window row / column.  The dv plane left in
+ * scratch[0 : B c_out ch cw] is k_bwd_dv's BIT FOR BIT for every finite or infinite membrane (same operations in the same order),
+ * so the weight gradient, the reduction, d_outW and d_outb behind it are the bits of the same call without the flag.  A NaN
+ * membrane is outside that contract (k_bwd_dv lets a NaN element win beside its window's maximum; k_bwd_dv_pool picks one winner).
+ * Served: pool_h, pool_w in {1, 2, 3}, not both 1; ch >= pool_h, cw >= pool_w; target <= 32; c_out ph pw and c_out ch cw below
+ * 2^31 (less a margin of one workgroup / one plane row); at most 65535 chunks of 8 samples.  The conv's own parameters do not
+ * enter.  The flag on a layer without pooling ("k_bwd_dv_nopool<..>") or on an unserved layer ("k_bwd_dv") is accepted and changes
+ * nothing.  v, scratch, g_v, g_pv and i2o_W need 4-byte alignment only (one form, scalar loads); g_p, g_pv and g_v may each be NULL.
+ * DCLL_ERR_INVALID before anything is launched and before B is looked at: an unknown flag bit, an unknown path, bands != 0 with a
+ * path other than DCLL_BWD_BANDS, (open form) a NULL part / nchunk.  B == 0 with those valid: DCLL_OK, nothing else is looked at.
+ * Launch log with the flag on a served layer: "k_bwd_dv_pool", then as without the flag.
+ * dcll_bwd_dv_pool_served: host only, launches nothing; 1 served, 0 not served (B < 1 included), a negative DCLL_ERR_* for an
+ * invalid descriptor.
+ */
+#define DCLL_BWD_DEFAULT 0   /* dcll_conv_lif_backward        */
+#define DCLL_BWD_ANY     1   /* dcll_conv_lif_backward_any    */
+#define DCLL_BWD_WIDE    2   /* dcll_conv_lif_backward_wide   */
+#define DCLL_BWD_SLAB    3   /* dcll_conv_lif_backward_slab   */
+#define DCLL_BWD_BANDS   4   /* dcll_conv_lif_backward_bands  */
+#define DCLL_BWD_POOL_DV 1u
+int dcll_conv_lif_backward_ex(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                              const float *g_p, const float *g_o, const float *g_pv, const float *g_v, const float *i2o_W,
+                              float *dW, float *db, float *d_outW, float *d_outb, float *scratch, int64_t scratch_floats,
+                              int32_t B, int32_t path, int32_t bands, uint32_t flags, void *stream);
+int dcll_conv_lif_backward_ex_open(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                                   const float *g_p, const float *g_o, const float *g_pv, const float *g_v, const float *i2o_W,
+                                   float *d_outW, float *d_outb, float *scratch, int64_t scratch_floats, int32_t B,
+                                   const float **part, int32_t *nchunk, int32_t path, int32_t bands, uint32_t flags, void *stream);
+int32_t dcll_bwd_dv_pool_served(const dcll_conv_desc *d, int32_t B);
+
 #ifdef __cplusplus
 }
 #endif

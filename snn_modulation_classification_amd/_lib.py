@@ -194,6 +194,10 @@ SIGNATURES = {
     "dcll_conv_lif_backward_w3_ex": (_I32, [_DP] + [_P] * 13 + [_I64, _I32, ctypes.c_uint32, _P]),
     "dcll_conv_lif_backward_w3_ex_open": (_I32, [_DP] + [_P] * 11 + [_I64, _I32, ctypes.POINTER(ctypes.c_void_p), _IP,
                                                  ctypes.c_uint32, _P]),
+    "dcll_conv_lif_backward_ex": (_I32, [_DP] + [_P] * 13 + [_I64, _I32, _I32, _I32, ctypes.c_uint32, _P]),
+    "dcll_conv_lif_backward_ex_open": (_I32, [_DP] + [_P] * 11 + [_I64, _I32, ctypes.POINTER(ctypes.c_void_p), _IP,
+                                              _I32, _I32, ctypes.c_uint32, _P]),
+    "dcll_bwd_dv_pool_served": (_I32, [_DP, _I32]),
 }
 
 

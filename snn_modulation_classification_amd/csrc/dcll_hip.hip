@@ -3681,7 +3681,8 @@ static int conv_lif_backward_impl(const dcll_conv_desc *d, const float *eps1, co
                                   const float *i2o_W, float *dW, float *db, float *d_outW, float *d_outb,
                                   float *scratch, int64_t scratch_floats, int32_t B, void *stream,
                                   const float **open_part, int32_t *open_nchunk, bool dv_done = false,
-                                  wgrad_sel sel = WGRAD_DEFAULT, bool dv_w3 = false, int32_t bands = 0)
+                                  wgrad_sel sel = WGRAD_DEFAULT, bool dv_w3 = false, int32_t bands = 0,
+                                  bool dv_pool = false)
 {
     // WGRAD_ANY: the weight gradient by k_bwd_wgrad_any (dcll_bwd_any.hip) whatever the geometry — none of the specialised
     // kernels, and neither the tap nor the row-width limit of the generic k_bwd_wgrad.  WGRAD_W3: by k_bwd_wgrad_w3
@@ -3695,6 +3696,8 @@ static int conv_lif_backward_impl(const dcll_conv_desc *d, const float *eps1, co
     // planes whose sample the three kernels above cannot stage (dcll_conv_lif_backward_bands hands the layers and band counts
     // that dcll_conv_lif_backward_slab serves to the selectors above before it gets here)
     // dv_w3 (with WGRAD_W3 / WGRAD_W3F only): the dv plane by k_bwd_dv_w3 (dcll_step_w3.hip) instead of k_bwd_dv, same bits
+    // dv_pool (dcll_conv_lif_backward_ex): the dv plane of a layer that pools by k_bwd_dv_pool (dcll_bwd_dv_pool.hip) instead of
+    // k_bwd_dv where that kernel serves the layer, same bits; a layer without pooling or outside its served set: unchanged
     const bool any = sel == WGRAD_ANY, wide = sel == WGRAD_WIDE, slab = sel == WGRAD_SLAB, w3f = sel == WGRAD_W3F, w3 = sel == WGRAD_W3 || w3f;
     const bool band = sel == WGRAD_BAND;
     int rc = check_desc(d);
@@ -3766,8 +3769,9 @@ static int conv_lif_backward_impl(const dcll_conv_desc *d, const float *eps1, co
     } else {
         const char *form = nullptr;
         if (dv_w3 && w3 && (rc = dcll_launch_bwd_dv_w3(d, v, g_p, g_pv, g_v, i2o_W, scratch, B, st, &form)) != DCLL_OK) return rc;
+        if (!form && dv_pool && (rc = dcll_launch_bwd_dv_pool(d, v, g_p, g_pv, g_v, i2o_W, scratch, B, st, &form)) != DCLL_OK) return rc;
         if (form) dv_form = form;
-        else        // (without dv_w3, or a layer k_bwd_dv_w3 leaves to the generic kernel: more than 32 readout rows)
+        else        // (without dv_w3 / dv_pool, or a layer they leave to the generic kernel: more than 32 readout rows)
             hipLaunchKernelGGL(k_bwd_dv, dim3(nblk(nconv, 256)), dim3(256), 0, st, *d, ch, cw, ph, pw, v, g_p, g_pv, g_v, i2o_W,
                                scratch, nconv);
     }
@@ -4079,6 +4083,56 @@ extern "C" int dcll_conv_lif_backward_w3_ex_open(const dcll_conv_desc *d, const 
     return conv_lif_backward_impl(d, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, nullptr, nullptr, d_outW, d_outb, scratch,
                                   scratch_floats, B, stream, part, nchunk, false,
                                   (flags & DCLL_W3_FIRST_WGRAD) ? WGRAD_W3F : WGRAD_W3, (flags & DCLL_W3_DV) != 0);
+}
+
+// found by symbol lookup (the ABI version stays 10): the calls above behind ONE pair of entry points.  path names the call
+// (DCLL_BWD_DEFAULT: dcll_conv_lif_backward, _ANY, _WIDE, _SLAB, _BANDS: that suffix; bands is the argument of _BANDS and must be 0
+// elsewhere); flags == 0 is that call — bits, launch log, refusals, scratch rule.  DCLL_BWD_POOL_DV replaces its "k_bwd_dv" launch
+// by k_bwd_dv_pool (dcll_bwd_dv_pool.hip) where dcll_bwd_dv_pool_served() holds: a bit-identical dv plane, so everything behind it
+// is unchanged too.  An unknown flag bit, an unknown path, bands without DCLL_BWD_BANDS: DCLL_ERR_INVALID before B is looked at;
+// B == 0 then: DCLL_OK
+static int bwd_ex_sel(const dcll_conv_desc *d, int32_t path, int32_t bands, uint32_t flags, wgrad_sel *sel, const char *who)
+{
+    if (flags & ~(uint32_t)DCLL_BWD_POOL_DV) return fail(DCLL_ERR_INVALID, "unknown flag bits", who);
+    if (path < DCLL_BWD_DEFAULT || path > DCLL_BWD_BANDS) return fail(DCLL_ERR_INVALID, "unknown path", who);
+    if (bands != 0 && path != DCLL_BWD_BANDS) return fail(DCLL_ERR_INVALID, "bands is an argument of DCLL_BWD_BANDS only (0 elsewhere)", who);
+    *sel = path == DCLL_BWD_DEFAULT ? WGRAD_DEFAULT
+           : path == DCLL_BWD_ANY   ? WGRAD_ANY
+           : path == DCLL_BWD_WIDE  ? (d && d->c_out <= 32 ? WGRAD_ANY : WGRAD_WIDE)
+           : path == DCLL_BWD_SLAB  ? slab_sel(d)
+                                    : band_sel(d, bands);
+    return DCLL_OK;
+}
+
+extern "C" int dcll_conv_lif_backward_ex(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                                         const float *g_p, const float *g_o, const float *g_pv, const float *g_v,
+                                         const float *i2o_W, float *dW, float *db, float *d_outW, float *d_outb,
+                                         float *scratch, int64_t scratch_floats, int32_t B, int32_t path, int32_t bands,
+                                         uint32_t flags, void *stream)
+{
+    wgrad_sel sel;
+    const int rc = bwd_ex_sel(d, path, bands, flags, &sel, "dcll_conv_lif_backward_ex");
+    if (rc) return rc;
+    if (B == 0) return DCLL_OK;
+    return conv_lif_backward_impl(d, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, dW, db, d_outW, d_outb, scratch,
+                                  scratch_floats, B, stream, nullptr, nullptr, false, sel, false, bands,
+                                  (flags & DCLL_BWD_POOL_DV) != 0);
+}
+
+extern "C" int dcll_conv_lif_backward_ex_open(const dcll_conv_desc *d, const float *eps1, const float *v, const float *pv_pooled,
+                                              const float *g_p, const float *g_o, const float *g_pv, const float *g_v,
+                                              const float *i2o_W, float *d_outW, float *d_outb, float *scratch,
+                                              int64_t scratch_floats, int32_t B, const float **part, int32_t *nchunk,
+                                              int32_t path, int32_t bands, uint32_t flags, void *stream)
+{
+    wgrad_sel sel;
+    const int rc = bwd_ex_sel(d, path, bands, flags, &sel, "dcll_conv_lif_backward_ex_open");
+    if (rc) return rc;
+    if (!part || !nchunk) return fail(DCLL_ERR_INVALID, "dcll_conv_lif_backward_ex_open: null part / nchunk");
+    if (B == 0) return DCLL_OK;
+    return conv_lif_backward_impl(d, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, nullptr, nullptr, d_outW, d_outb, scratch,
+                                  scratch_floats, B, stream, part, nchunk, false, sel, false, bands,
+                                  (flags & DCLL_BWD_POOL_DV) != 0);
 }
 
 // dcll_conv_lif_backward_open for n layers — the slices of one learning timestep — with their dv launches as ONE launch

@@ -256,6 +256,13 @@ __attribute__((visibility("hidden")))
 int dcll_launch_bwd_dv_w3(const dcll_conv_desc *d, const float *v, const float *g_p, const float *g_pv, const float *g_v,
                           const float *i2o_W, float *gvf, int32_t B, hipStream_t st, const char **form);
 
+// k_bwd_dv_pool (dcll_bwd_dv_pool.hip): the dv plane of a layer that pools (pool sizes 1 .. 3, not both 1), a streaming form of
+// k_bwd_dv: a thread owns a pooled window.  Launches and sets *form to the kernel's name for the launch log; *form == nullptr: not
+// served (dcll_bwd_dv_pool_served is the predicate), nothing launched
+__attribute__((visibility("hidden")))
+int dcll_launch_bwd_dv_pool(const dcll_conv_desc *d, const float *v, const float *g_p, const float *g_pv, const float *g_v,
+                            const float *i2o_W, float *gvf, int32_t B, hipStream_t st, const char **form);
+
 // dense twins (dcll_dense.hip): one step as an fp32-MFMA GEMM on the updated traces; all T steps with the state on chip
 __attribute__((visibility("hidden")))
 int dcll_launch_dense_mfma(const dcll_dense_desc *d, const float *eps1, const float *W, const float *b, float *arp,

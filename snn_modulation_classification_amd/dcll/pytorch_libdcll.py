@@ -1231,6 +1231,8 @@ class DCLLBase(nn.Module):
     w3_learning_path = False        # _learn_tail: dcll_conv_lif_backward_w3[_open] (k_bwd_wgrad_w3); set by ConvNetwork.w3_step_path
     w3_first_wgrad = False          # with w3_learning_path: dcll_conv_lif_backward_w3f[_open] (the c_in 1 layer on k_bwd_wgrad_w3f);
                                     # set by ConvNetwork.w3_first_wgrad
+    pool_dv = False                 # _learn_tail: the backward call through dcll_conv_lif_backward_ex[_open] with DCLL_BWD_POOL_DV (the dv
+                                    # plane of a pooling layer from k_bwd_dv_pool, bit-identical to k_bwd_dv's); set by ConvNetwork.pool_dv_path
     w3_dv = False                   # with w3_learning_path: dcll_conv_lif_backward_w3_ex[_open] with DCLL_W3_DV (the dv plane from
                                     # k_bwd_dv_w3, bit-identical to k_bwd_dv's); set by ConvNetwork.w3_dv_path
 
@@ -1341,7 +1343,8 @@ class DCLLBase(nn.Module):
                                   defer=defer_backward if open_reduce else None, any_path=self.any_learning_path,
                                   w3_path=self.w3_learning_path, w3_first=self.w3_first_wgrad, w3_dv=self.w3_dv,
                                   wide_path=self.wide_learning_path, slab_path=self.slab_learning_path,
-                                  band_path=self.band_learning_path is not False, bands=self._band_count())
+                                  band_path=self.band_learning_path is not False, bands=self._band_count(),
+                                  pool_dv=self.pool_dv)
         return loss
 
     def _grads_into_slab(self):

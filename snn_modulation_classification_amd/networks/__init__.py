@@ -313,6 +313,7 @@ class ConvNetwork(torch.nn.Module):
             sig.append(bool(L.i2h.wide_step_path))
             sig.append(bool(L.i2h.slab_step_path))
             sig.append((bool(s.w3_learning_path), bool(L.i2h.w3_step_path), bool(s.w3_first_wgrad), bool(s.w3_dv)))
+            sig.append(bool(s.pool_dv))
             for t in s._adam_tensors(advance=False):
                 sig += [t['param'].data_ptr(), t['grad'].data_ptr(), t['exp_avg'].data_ptr(),
                         t['exp_avg_sq'].data_ptr(), t['weight_decay'], t['beta1'], t['beta2'], t['eps']]
@@ -1132,6 +1133,8 @@ class ConvNetwork(torch.nn.Module):
             raise ops._lib.DCLLUnsupported('w3_step_path cannot be combined with wide_step_path')
         if on and any(s.dclllayer.i2h.slab_step_path for s in self.dcll_slices):
             raise ops._lib.DCLLUnsupported('w3_step_path cannot be combined with slab_step_path')
+        if on and any(s.pool_dv for s in self.dcll_slices):
+            raise ops._lib.DCLLUnsupported('w3_step_path cannot be combined with pool_dv_path (w3_dv_path is its dv kernel)')
         if on and not self.w3_step_supported():
             raise ops._lib.DCLLUnsupported('dcll_conv_lif_step_w3 / dcll_conv_lif_backward_w3 do not serve every layer of this '
                                            'network')
@@ -1175,6 +1178,25 @@ class ConvNetwork(torch.nn.Module):
             raise ops._lib.DCLLUnsupported('w3_dv_path needs w3_step_path (set it first)')
         for s in self.dcll_slices:              # (part of _graph_signature: a captured timestep of the other path is retaken)
             s.w3_dv = on
+
+    @property
+    def pool_dv_path(self):
+        """True: every learning step makes its backward call through dcll_conv_lif_backward_ex[_open] with DCLL_BWD_POOL_DV — the path
+        is the one the learning-path switches select — so a layer that pools takes its dv plane from k_bwd_dv_pool (a streaming form
+        of k_bwd_dv: a thread owns a pooled window) where ops.bwd_dv_pool_supported holds; a layer without pooling, or an unserved
+        one, keeps its kernel.  The plane is bit-identical, so every gradient and the parameters after Adam are the bits of the same
+        network without it.  Combines with every learning path and every step path except w3_step_path (which has w3_dv_path):
+        setting it True under w3_step_path raises DCLLUnsupported and leaves it off, and so does w3_step_path = True under it.
+        Default False; switching it off is always allowed."""
+        return all(s.pool_dv for s in self.dcll_slices)
+
+    @pool_dv_path.setter
+    def pool_dv_path(self, on):
+        on = bool(on)
+        if on and any(s.w3_learning_path for s in self.dcll_slices):
+            raise ops._lib.DCLLUnsupported('pool_dv_path cannot be combined with w3_step_path (w3_dv_path is its dv kernel)')
+        for s in self.dcll_slices:              # (part of _graph_signature: a captured timestep of the other path is retaken)
+            s.pool_dv = on
 
     # -- the fused path of any plain conv network (k_lif_seq_any, ABI 8): opt-in, beside test_sequence ---------------------
     def sequence_any_supported(self, wide=False, bands=None, tiles=None, slabs=None):

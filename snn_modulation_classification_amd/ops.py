@@ -379,6 +379,18 @@ def backward_bands_plan(desc, B, bands=0):
     return dict(zip(("NB", "RB", "TPW", "PS", "NQ", "NS", "nsplit", "nchunk"), (int(v) for v in out)))
 
 
+def bwd_dv_pool_supported(desc, B=1):
+    """True if conv_lif_backward(pool_dv=True) takes this layer's dv plane from k_bwd_dv_pool at batch B: pool sizes 1 .. 3 (not
+    both 1) on a conv plane at least as large, at most 32 readout rows, index ranges (dcll_bwd_dv_pool_served; host only).  False:
+    the call keeps its own dv kernel.  An invalid descriptor raises."""
+    rc = int(_lib.get().dcll_bwd_dv_pool_served(ctypes.byref(desc), int(B)))
+    if rc < 0:
+        check(rc, "dcll_bwd_dv_pool_served")
+    return rc == 1
+
+
+BWD_PATH_DEFAULT, BWD_PATH_ANY, BWD_PATH_WIDE, BWD_PATH_SLAB, BWD_PATH_BANDS = 0, 1, 2, 3, 4   # `path` of dcll_conv_lif_backward_ex[_open]
+BWD_POOL_DV = 1                 # its flag bit DCLL_BWD_POOL_DV
 BWD_ANY_MAX_CHUNKS = 256        # batch chunks (partial rows) of k_bwd_wgrad_any, at most
 BWD_W3F_PB = 128                # pixels of a job of k_bwd_wgrad_w3f (the flattened B x h w stream): at most one partial row per job
 W3_FIRST_WGRAD, W3_DV = 1, 2    # flag bits of dcll_conv_lif_backward_w3_ex[_open] (DCLL_W3_FIRST_WGRAD, DCLL_W3_DV)
@@ -386,7 +398,7 @@ W3_FIRST_WGRAD, W3_DV = 1, 2    # flag bits of dcll_conv_lif_backward_w3_ex[_ope
 
 def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want_out, out=None, open_reduce=False, defer=None,
                       any_path=False, w3_path=False, w3_first=False, w3_dv=False, wide_path=False, slab_path=False,
-                      band_path=False, bands=0):
+                      band_path=False, bands=0, pool_dv=False):
     """Gradients of one layer step (dcll_conv_lif_backward) -> (dW, db, d_outW, d_outb).  `out`: optional dict with
     preallocated 'dW', 'db', 'd_outW', 'd_outb', 'bwd_scratch' (the learning loop writes into the parameters' .grad).
     `open_reduce`: dcll_conv_lif_backward_open — dW / db are NOT written yet; the partial rows of the weight gradient stay
@@ -412,7 +424,13 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
     on k_bwd_wgrad_band (fp32 MFMA, a sample in bands of conv-output rows; backward_bands_supported).  `bands` (with `band_path`;
     alone it raises): 0 the library's rule — a layer the `slab_path` serves runs that path, same bits and launch log —, 1 the
     `slab_path` call itself, N >= 2 exactly N bands.  The partial-row scratch is sized from backward_bands_plan's nchunk.  `defer` as
-    for `any_path`; combined with any other path it raises."""
+    for `any_path`; combined with any other path it raises.
+    `pool_dv`: the call goes through dcll_conv_lif_backward_ex[_open] with DCLL_BWD_POOL_DV and the path the other arguments select —
+    the dv plane of a layer that pools from k_bwd_dv_pool instead of k_bwd_dv where bwd_dv_pool_supported holds, bit for bit the same
+    plane; an unserved layer is unchanged, and for a layer without pooling the call is made exactly as without `pool_dv`; the scratch
+    size is unchanged.  With `defer` the slice's own open call is launched at once, as for `any_path`.  Combined with `w3_path` it raises (that path has `w3_dv`)."""
+    if pool_dv and w3_path:
+        raise ValueError("conv_lif_backward(pool_dv=True) cannot be combined with w3_path=True (w3_dv is that path's dv kernel)")
     if band_path and (any_path or w3_path or wide_path or slab_path):
         raise ValueError("conv_lif_backward(band_path=True) cannot be combined with any_path=True, w3_path=True, wide_path=True or slab_path=True")
     if bands and not band_path:
@@ -483,7 +501,13 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
     flags = ()
     if w3_dv:       # (the flag-word entry points; without w3_dv the calls above are made as before)
         fn, flags = "dcll_conv_lif_backward_w3_ex", (W3_DV | (W3_FIRST_WGRAD if w3_first else 0),)
-    if defer is not None and not any_path and not w3_path and not wide_path and not slab_path and not band_path:       # (open form, launched later with other layers': conv_lif_backward_open_multi)
+    if pool_dv and desc.pool_h == 1 and desc.pool_w == 1:
+        pool_dv = False     # (a layer without pooling: the flag changes nothing, so the call — its multi-layer form included — is made as before)
+    if pool_dv:     # (the path / flag-word entry points; without pool_dv the calls above are made as before)
+        path = (BWD_PATH_BANDS if band_path else BWD_PATH_SLAB if slab_path else BWD_PATH_WIDE if wide_path else
+                BWD_PATH_ANY if any_path else BWD_PATH_DEFAULT)
+        fn, band_arg, flags = "dcll_conv_lif_backward_ex", (), (path, int(bands), BWD_POOL_DV)
+    if defer is not None and not any_path and not w3_path and not wide_path and not slab_path and not band_path and not pool_dv:       # (open form, launched later with other layers': conv_lif_backward_open_multi)
         item = _lib.BwdItem(ctypes.pointer(desc), ptr(eps1), ptr(v), ptr(pv_pooled), ptr(gp_), ptr(go_), ptr(gpv_), ptr(gv_),
                             ptr(i2o_W), ptr(d_outW), ptr(d_outb), ptr(scratch), n_scratch, B, 0, None, 0, 0)
         defer.append(dict(item=item, out=out, desc=desc, dW=dW, db=db, scratch=scratch,

@@ -211,6 +211,13 @@ def parse_args(argv=None):
                         'per timestep at B = 512 (1.62-1.64x), 1.050-1.088 -> 0.883-0.913 ms at B = 64 (1.15-1.23x); layer 0\'s dv kernel '
                         '829.5 -> 100.1 us at B = 512 (0.85 of the copy rate); the open backward call of every one of the seven layers is '
                         'faster at both batch sizes, none slower.  Table: profiles/r15_w3_dv_timing.txt')
+    p.add_argument('--pool_dv_path', action='store_true',
+                   help='opt in: every learning step\'s backward call goes through dcll_conv_lif_backward_ex with DCLL_BWD_POOL_DV, '
+                        'so a layer that pools (pool sizes 1-3) takes its dv plane from k_bwd_dv_pool (a streaming form of k_bwd_dv: a '
+                        'thread owns a pooled window, readout weights in registers) instead of the generic k_bwd_dv; the plane, and with '
+                        'it every gradient, is bit-identical.  Combines with every learning and step path except --w3_step_path '
+                        '(which has --w3_dv_path); ignored with a notice there and where no layer of the network pools.  '
+                        'Table: profiles/r28_pool_dv_timing.txt')
     p.add_argument('--gpus', type=int, default=1, metavar='N',
                    help='ranks (one process per GPU): every batch is sharded over them, the local-learning gradients are '
                         'averaged over the ranks every timestep (one bucketed all-reduce)')
@@ -276,6 +283,7 @@ def main(argv=None):
     _opt_in_wide_learning(net, args)
     _opt_in_slab_learning(net, args)
     _opt_in_band_learning(net, args)
+    _opt_in_pool_dv(net, args)
     parallel.freeze_startup_heap()          # (a full GC pass over the start-up heap costs ~100 ms inside the T-loop)
 
     if not args.no_save:
@@ -640,6 +648,19 @@ def _opt_in_w3_step(net, args):
             print('--w3_dv_path ignored: --w3_step_path is not in effect on this network')
 
 
+def _opt_in_pool_dv(net, args):
+    """--pool_dv_path: the learning step's backward calls through dcll_conv_lif_backward_ex with DCLL_BWD_POOL_DV (k_bwd_dv_pool for
+    the layers that pool); runs behind the other opt-ins, whose paths it keeps."""
+    if not getattr(args, 'pool_dv_path', False):
+        return
+    if net.w3_step_path:
+        print('--pool_dv_path ignored: --w3_step_path is in effect (its dv kernel is --w3_dv_path)')
+    elif not any(tuple(s.dclllayer.pooling) != (1, 1) for s in net.dcll_slices):
+        print('--pool_dv_path ignored: no layer of this network pools')
+    else:
+        net.pool_dv_path = True
+
+
 def main_mnist(args):
     """--data MNIST (reference train.py:118-131): 28x28 images as frozen Poisson spike trains (image2spiketrain,
     gain 100), 10 classes, any conv spec that fits 28x28 (networks/mnist_conv.yaml), per-step protocol for learning
@@ -671,6 +692,7 @@ def main_mnist(args):
     _opt_in_wide_learning(net, args)
     _opt_in_slab_learning(net, args)
     _opt_in_band_learning(net, args)
+    _opt_in_pool_dv(net, args)
     use_wide = _opt_in_wide_sequence(net, args, net.sequence_supported())      # (the condition of --any_sequence_path below)
     use_bands = _opt_in_band_sequence(net, args, net.sequence_supported())
     use_tiles = _opt_in_tile_sequence(net, args, net.sequence_supported())
