@@ -245,6 +245,45 @@ int dcll_grad_reduce_adam(const dcll_grad_parts *layers, int32_t n_layers, const
                           int32_t n_tensors, const float *dyn, void *stream);
 
 /*
+ * dcll_optim_step / dcll_grad_reduce_optim — dcll_adam_step / dcll_grad_reduce_adam with the update chosen per tensor by `kind`:
+ * torch.optim.Adam, AdamW, Adamax and SGD (torch 2.10's _single_tensor_* functions; maximize False), kinds mixed freely in one
+ * launch.  fp32, every operation rounded separately, division and sqrtf correctly rounded.  g = grad + weight_decay * p for the
+ * coupled kinds (ADAM, ADAMAX, SGD), g = grad for ADAMW.
+ *   ADAM    s0 = exp_avg, s1 = exp_avg_sq, with DCLL_OPT_AMSGRAD s2 = max_exp_avg_sq.  Without the flag: dcll_adam_step's
+ *           update, the same bits.  With it: s2 = max(s2, v) and the denominator is sqrt(s2) / sqrt(bc2) + eps.
+ *   ADAMW   as ADAM, after p = p * c, c = (float)(1 - lr * weight_decay) (host, float64 on the struct's floats).
+ *   ADAMAX  s0 = exp_avg, s1 = exp_inf: m = lerp(m, g, 1 - beta1); u = max(u * beta2, |g| + eps); p -= (lr / bc1) * (m / u).
+ *   SGD     s0 = momentum_buffer (NULL when momentum is 0): buf = DCLL_OPT_FIRST ? g : buf * momentum + (1 - dampening) * g;
+ *           g' = DCLL_OPT_NESTEROV ? g + momentum * buf : buf (without momentum g' = g); p -= lr * g'.
+ *           DCLL_OPT_FIRST: the caller's mark of the update that creates the buffer (buf = g bit for bit, no product with the buffer's old content).
+ * h0 / h1: beta1 / beta2 (ADAM, ADAMW, ADAMAX), momentum / dampening (SGD).  max(a, b) is torch.maximum's: a NaN wins.
+ * dyn: NULL, or DEVICE memory, DCLL_OPTIM_DYN floats per tensor, read at execution time (the form a captured timestep replays;
+ * `lr` and `step` of the structs are then ignored): (lr, 1 / bc1, 1 / sqrt(bc2), c) for ADAM / ADAMW (c unused by ADAM),
+ * (lr, 1 / bc1, 0, 0) for ADAMAX, (lr, (float)(1 - dampening), 0, 0) for SGD — the values the host computes without dyn
+ * (float64 on the struct's floats, cast once).
+ * dcll_grad_reduce_optim: `layers` as dcll_grad_reduce_adam (adam_w / adam_b index `t`), the same partial-row grouping and
+ * order: dW / db are its bits.  Launch log: "k_optim_multi" / "k_grad_reduce_optim".
+ * DCLL_ERR_INVALID before any launch: a state pointer the kind needs is NULL, unknown kind or flag bits (NESTEROV / FIRST on
+ * a kind other than SGD or without momentum, AMSGRAD on ADAMAX / SGD included), step < 1, n < 0, more than
+ * DCLL_OPTIM_MAX_TENSORS tensors or DCLL_REDUCE_MAX_LAYERS layers, a tensor referred to by two layers, sizes that do not match
+ * c_out * (rowlen - 1) / c_out.
+ */
+enum { DCLL_OPT_ADAM = 0, DCLL_OPT_ADAMW = 1, DCLL_OPT_ADAMAX = 2, DCLL_OPT_SGD = 3 };
+enum { DCLL_OPT_AMSGRAD = 1, DCLL_OPT_NESTEROV = 2, DCLL_OPT_FIRST = 4 };
+#define DCLL_OPTIM_MAX_TENSORS 8
+#define DCLL_OPTIM_DYN 4      /* floats per tensor in `dyn` */
+typedef struct dcll_optim_tensor {
+    float *param; const float *grad;
+    float *s0, *s1, *s2;      /* state by kind, above; unused ones NULL */
+    int64_t n, step;
+    int32_t kind, flags;
+    float lr, weight_decay, h0, h1, eps;
+} dcll_optim_tensor;
+int dcll_optim_step(const dcll_optim_tensor *t, int32_t n, const float *dyn, void *stream);
+int dcll_grad_reduce_optim(const dcll_grad_parts *layers, int32_t n_layers,
+                           const dcll_optim_tensor *t, int32_t n, const float *dyn, void *stream);
+
+/*
  * dcll_conv_lif_backward_open for SEVERAL layers — the slices of one learning timestep — in one call (ABI 6): where all of
  * them are layers without pooling with the same readout-width class their dv launches (max-pool routing / i2o^T / sigmoid')
  * run as ONE launch, then the weight / output_ gradient kernels layer by layer.  Each field is the argument of that name of

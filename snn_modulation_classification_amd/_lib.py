@@ -47,6 +47,14 @@ class AdamTensor(ctypes.Structure):
                 ("beta2", ctypes.c_float), ("eps", ctypes.c_float)]
 
 
+class OptimTensor(ctypes.Structure):
+    """dcll_optim_tensor"""
+    _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("s0", ctypes.c_void_p), ("s1", ctypes.c_void_p),
+                ("s2", ctypes.c_void_p), ("n", ctypes.c_int64), ("step", ctypes.c_int64), ("kind", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("lr", ctypes.c_float), ("weight_decay", ctypes.c_float), ("h0", ctypes.c_float),
+                ("h1", ctypes.c_float), ("eps", ctypes.c_float)]
+
+
 class GradParts(ctypes.Structure):
     """dcll_grad_parts"""
     _fields_ = [("part", ctypes.c_void_p), ("dW", ctypes.c_void_p), ("db", ctypes.c_void_p), ("rowlen", ctypes.c_int64),
@@ -91,6 +99,9 @@ class IQTail(ctypes.Structure):
 ACT_NONE, ACT_SIGMOID = 0, 1
 ADAM_MAX_TENSORS = 8
 REDUCE_MAX_LAYERS = 4
+OPTIM_MAX_TENSORS, OPTIM_DYN = 8, 4
+OPT_ADAM, OPT_ADAMW, OPT_ADAMAX, OPT_SGD = 0, 1, 2, 3
+OPT_AMSGRAD, OPT_NESTEROV, OPT_FIRST = 1, 2, 4
 LOSS_SMOOTH_L1, LOSS_MSE = 0, 1
 
 _P, _I32, _I64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
@@ -114,6 +125,8 @@ SIGNATURES = {
     "dcll_adam_step_dyn": (_I32, [ctypes.POINTER(AdamTensor), _I32, _P, _P]),
     "dcll_conv_lif_backward_open": (_I32, [_DP] + [_P] * 11 + [_I64, _I32, ctypes.POINTER(ctypes.c_void_p), _IP, _P]),
     "dcll_grad_reduce_adam": (_I32, [ctypes.POINTER(GradParts), _I32, ctypes.POINTER(AdamTensor), _I32, _P, _P]),
+    "dcll_optim_step": (_I32, [ctypes.POINTER(OptimTensor), _I32, _P, _P]),
+    "dcll_grad_reduce_optim": (_I32, [ctypes.POINTER(GradParts), _I32, ctypes.POINTER(OptimTensor), _I32, _P, _P]),
     "dcll_conv_lif_backward_open_multi": (_I32, [ctypes.POINTER(BwdItem), _I32, _P]),
     "dcll_cells_to_planes": (_I32, [_P, _P, _I64, _I32, _P]),
     "dcll_dense_lif_step": (_I32, [_DDP] + [_P] * 16 + [_I32, _P]),

@@ -292,18 +292,34 @@ __device__ __forceinline__ void adam_element(const adam_args &a, int k, long i, 
     const dcll_adam_tensor &t = a.t[k];
     adam_update(a, k, i, grad, t.param[i], t.exp_avg[i], t.exp_avg_sq[i]);
 }
+// torch's lerp(m, g, w)
+__device__ __forceinline__ float lerp_torch(float m, float g, float w)
+{
+    return w < 0.5f ? m + w * (g - m) : g - (g - m) * (1.0f - w);
+}
+// torch.maximum: a NaN wins
+__device__ __forceinline__ float max_torch(float a, float b) { return (a > b || a != a) ? a : b; }
+// Adam on a gradient that already holds its decay, in two halves (adam_update and the ADAM / ADAMW kinds of optim_update): the
+// moments, then the step from the moment under the root (v; with amsgrad its running maximum)
+__device__ __forceinline__ void adam_moments(float g, float beta1, float beta2, float &m, float &v)
+{
+    m = lerp_torch(m, g, 1.0f - beta1);
+    v = v * beta2 + ((1.0f - beta2) * g) * g;
+}
+__device__ __forceinline__ float adam_step_from(float p, float m, float vroot, float eps, float lr, float ibc1, float isbc2)
+{
+    const float denom = sqrtf(vroot) * isbc2 + eps;
+    return p - (lr * ibc1) * (m / denom);
+}
 // (parameter and moments already in registers: k_grad_reduce_adam requests them before it adds the partial rows)
 __device__ __forceinline__ void adam_update(const adam_args &a, int k, long i, float grad, float p, float m, float v)
 {
     const dcll_adam_tensor &t = a.t[k];
     const float g = grad + t.weight_decay * p;
-    const float w = 1.0f - t.beta1;
-    m = w < 0.5f ? m + w * (g - m) : g - (g - m) * (1.0f - w);                 // torch's lerp
-    v = v * t.beta2 + ((1.0f - t.beta2) * g) * g;
+    adam_moments(g, t.beta1, t.beta2, m, v);
     const float lr = a.dyn ? a.dyn[3 * k] : t.lr;
     const float ibc1 = a.dyn ? a.dyn[3 * k + 1] : a.inv_bc1[k], isbc2 = a.dyn ? a.dyn[3 * k + 2] : a.inv_sqrt_bc2[k];
-    const float denom = sqrtf(v) * isbc2 + t.eps;
-    p = p - (lr * ibc1) * (m / denom);
+    p = adam_step_from(p, m, v, t.eps, lr, ibc1, isbc2);
     t.exp_avg[i] = m;
     t.exp_avg_sq[i] = v;
     t.param[i] = p;
@@ -385,6 +401,29 @@ struct reduce_adam_args {
     int n_layers;
 };
 
+// the share of group `grp` (of GR) in gradient element i of a layer: its partial rows added in chunk order (k_grad_reduce_adam and
+// k_grad_reduce_optim: the same bits)
+__device__ __forceinline__ float partial_rows_sum(const dcll_grad_parts &P, int GR, int grp, long i, long total)
+{
+    float acc = 0.0f;
+    if (i < total && grp < GR) {
+        const int per = (P.nchunk + GR - 1) / GR, c0 = grp * per, c1 = min(P.nchunk, c0 + per);
+        const float *src = P.part + i;
+        int c = c0;
+        if (GR > 1) {
+            for (; c + 8 <= c1; c += 8) {                     // eight loads in flight, added in chunk order
+                float t[8];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) t[q] = src[(long)(c + q) * total];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) acc += t[q];
+            }
+        }
+        for (; c < c1; ++c) acc += src[(long)c * total];
+    }
+    return acc;
+}
+
 __global__ __launch_bounds__(1024) void k_grad_reduce_adam(reduce_adam_args ra)
 {
     __shared__ float red[16][64];
@@ -418,22 +457,7 @@ __global__ __launch_bounds__(1024) void k_grad_reduce_adam(reduce_adam_args ra)
         m0 = ra.a.t[kt].exp_avg[e];
         v0 = ra.a.t[kt].exp_avg_sq[e];
     }
-    float acc = 0.0f;
-    if (i < total && grp < GR) {
-        const int per = (P.nchunk + GR - 1) / GR, c0 = grp * per, c1 = min(P.nchunk, c0 + per);
-        const float *src = P.part + i;
-        int c = c0;
-        if (GR > 1) {
-            for (; c + 8 <= c1; c += 8) {                     // eight loads in flight, added in chunk order
-                float t[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) t[q] = src[(long)(c + q) * total];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) acc += t[q];
-            }
-        }
-        for (; c < c1; ++c) acc += src[(long)c * total];
-    }
+    const float acc = partial_rows_sum(P, GR, grp, i, total);
     red[grp][lane] = acc;
     __syncthreads();
     if (grp != 0 || i >= total) return;
@@ -442,6 +466,38 @@ __global__ __launch_bounds__(1024) void k_grad_reduce_adam(reduce_adam_args ra)
     if (isw) P.dW[e] = tot;
     else if (P.db) P.db[co] = tot;
     if (kt >= 0) adam_update(ra.a, kt, e, tot, p0, m0, v0);
+}
+
+// the layers of a reduce launch, checked against the tensors they refer to (taken[idx]: a layer's thread updates tensor idx) ->
+// L, lfirst (64 gradient elements per workgroup), groups; dcll_grad_reduce_adam and dcll_grad_reduce_optim
+template <class Tensor>
+static int reduce_fill(const dcll_grad_parts *layers, int32_t n_layers, const Tensor *tensors, int32_t n_tensors, bool *taken,
+                       dcll_grad_parts *L, long *lfirst, int *groups, long *blocks_out, const char *who)
+{
+    long blocks = 0;
+    for (int l = 0; l < n_layers; ++l) {
+        const dcll_grad_parts &P = layers[l];
+        if (!P.part || !P.dW || P.nchunk < 1 || P.c_out < 1 || P.rowlen < 2)
+            return fail(DCLL_ERR_INVALID, "bad layer entry", who);
+        for (int idx : {P.adam_w, P.adam_b}) {
+            if (idx < -1 || idx >= n_tensors) return fail(DCLL_ERR_INVALID, "tensor index out of range", who);
+            if (idx >= 0) {
+                if (taken[idx]) return fail(DCLL_ERR_INVALID, "a tensor is referred to twice", who);
+                taken[idx] = true;
+            }
+        }
+        if (P.adam_w >= 0 && tensors[P.adam_w].n != (int64_t)P.c_out * (P.rowlen - 1))
+            return fail(DCLL_ERR_INVALID, "weight tensor size != c_out * (rowlen - 1)", who);
+        if (P.adam_b >= 0 && tensors[P.adam_b].n != P.c_out)
+            return fail(DCLL_ERR_INVALID, "bias tensor size != c_out", who);
+        L[l] = P;
+        groups[l] = P.nchunk >= 64 ? 16 : P.nchunk >= 16 ? 4 : 1;
+        lfirst[l] = blocks;
+        blocks += ((long)P.c_out * P.rowlen + 63) / 64;
+    }
+    lfirst[n_layers] = blocks;
+    *blocks_out = blocks;
+    return DCLL_OK;
 }
 
 extern "C" int dcll_grad_reduce_adam(const dcll_grad_parts *layers, int32_t n_layers, const dcll_adam_tensor *tensors,
@@ -456,31 +512,12 @@ extern "C" int dcll_grad_reduce_adam(const dcll_grad_parts *layers, int32_t n_la
     reduce_adam_args ra;
     bool taken[DCLL_ADAM_MAX_TENSORS] = {false};
     long blocks = 0;
-    for (int l = 0; l < n_layers; ++l) {
-        const dcll_grad_parts &P = layers[l];
-        if (!P.part || !P.dW || P.nchunk < 1 || P.c_out < 1 || P.rowlen < 2)
-            return fail(DCLL_ERR_INVALID, "dcll_grad_reduce_adam: bad layer entry");
-        for (int idx : {P.adam_w, P.adam_b}) {
-            if (idx < -1 || idx >= n_tensors) return fail(DCLL_ERR_INVALID, "dcll_grad_reduce_adam: tensor index out of range");
-            if (idx >= 0) {
-                if (taken[idx]) return fail(DCLL_ERR_INVALID, "dcll_grad_reduce_adam: a tensor is referred to twice");
-                taken[idx] = true;
-            }
-        }
-        if (P.adam_w >= 0 && tensors[P.adam_w].n != (int64_t)P.c_out * (P.rowlen - 1))
-            return fail(DCLL_ERR_INVALID, "dcll_grad_reduce_adam: weight tensor size != c_out * (rowlen - 1)");
-        if (P.adam_b >= 0 && tensors[P.adam_b].n != P.c_out)
-            return fail(DCLL_ERR_INVALID, "dcll_grad_reduce_adam: bias tensor size != c_out");
-        ra.L[l] = P;
-        ra.groups[l] = P.nchunk >= 64 ? 16 : P.nchunk >= 16 ? 4 : 1;
-        ra.lfirst[l] = blocks;
-        blocks += ((long)P.c_out * P.rowlen + 63) / 64;
-    }
-    ra.lfirst[n_layers] = blocks;
+    int rc = reduce_fill(layers, n_layers, tensors, n_tensors, taken, ra.L, ra.lfirst, ra.groups, &blocks, "dcll_grad_reduce_adam");
+    if (rc) return rc;
     ra.n_layers = n_layers;
     long ablocks = 0;
     if (n_tensors > 0) {
-        int rc = adam_fill(ra.a, tensors, n_tensors, dyn, 1024, taken, &ablocks, "dcll_grad_reduce_adam");
+        rc = adam_fill(ra.a, tensors, n_tensors, dyn, 1024, taken, &ablocks, "dcll_grad_reduce_adam");
         if (rc) return rc;
     } else {
         ra.a.n_tensors = 0;
@@ -491,6 +528,233 @@ extern "C" int dcll_grad_reduce_adam(const dcll_grad_parts *layers, int32_t n_la
     if (blocks + ablocks > 0x7fffffffL) return fail(DCLL_ERR_INVALID, "dcll_grad_reduce_adam: too many elements");
     hipLaunchKernelGGL(k_grad_reduce_adam, dim3((unsigned)(blocks + ablocks)), dim3(1024), 0, (hipStream_t)stream, ra);
     HIP_CHECK_LAUNCH("k_grad_reduce_adam");
+    return DCLL_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// k_optim_multi / k_grad_reduce_optim — k_adam_multi / k_grad_reduce_adam with the update chosen per tensor by its kind:
+// torch.optim.Adam, AdamW (both with or without amsgrad), Adamax and SGD, as torch's _single_tensor_* functions state them.  A
+// workgroup belongs to one tensor, so the kind is uniform in it.  The scalars that change from step to step (DCLL_OPTIM_DYN per
+// tensor: lr, 1 / bc1, 1 / sqrt(bc2), c for the Adam kinds; lr, 1 / bc1 for Adamax; lr, 1 - dampening for SGD) come from the
+// host (float64 on the struct's floats, cast once) or, with dyn, from device memory at execution time.
+// ------------------------------------------------------------------------------------------------------------
+struct optim_args {
+    dcll_optim_tensor t[DCLL_OPTIM_MAX_TENSORS];
+    long first[DCLL_OPTIM_MAX_TENSORS + 1];             // prefix sums of n, in blocks
+    float host[DCLL_OPTIM_MAX_TENSORS][DCLL_OPTIM_DYN]; // what dyn holds, for the form without it
+    const float *dyn;
+    int n_tensors;
+};
+
+// one function per kind: the update of element i, gradient, parameter and state (x0, x1, x2 = s0[i], s1[i], s2[i]) in registers
+__device__ __forceinline__ void adam_kinds(const dcll_optim_tensor &t, long i, float g, float p, float m, float v, float vmax,
+                                           float lr, float ibc1, float isbc2)
+{
+    adam_moments(g, t.h0, t.h1, m, v);
+    if (t.flags & DCLL_OPT_AMSGRAD) {
+        vmax = max_torch(vmax, v);
+        t.s2[i] = vmax;
+    } else {
+        vmax = v;
+    }
+    t.s0[i] = m;
+    t.s1[i] = v;
+    t.param[i] = adam_step_from(p, m, vmax, t.eps, lr, ibc1, isbc2);
+}
+__device__ __forceinline__ void optim_adam(const dcll_optim_tensor &t, long i, float grad, float p, float m, float v, float vmax,
+                                           float lr, float ibc1, float isbc2)
+{
+    adam_kinds(t, i, grad + t.weight_decay * p, p, m, v, vmax, lr, ibc1, isbc2);
+}
+__device__ __forceinline__ void optim_adamw(const dcll_optim_tensor &t, long i, float grad, float p, float m, float v, float vmax,
+                                            float lr, float ibc1, float isbc2, float c)
+{
+    adam_kinds(t, i, grad, p * c, m, v, vmax, lr, ibc1, isbc2);         // decoupled decay: p = p (1 - lr wd) first
+}
+__device__ __forceinline__ void optim_adamax(const dcll_optim_tensor &t, long i, float grad, float p, float m, float u, float lr,
+                                             float ibc1)
+{
+    const float g = grad + t.weight_decay * p;
+    m = lerp_torch(m, g, 1.0f - t.h0);
+    u = max_torch(u * t.h1, fabsf(g) + t.eps);
+    p = p - (lr * ibc1) * (m / u);
+    t.s0[i] = m;
+    t.s1[i] = u;
+    t.param[i] = p;
+}
+__device__ __forceinline__ void optim_sgd(const dcll_optim_tensor &t, long i, float grad, float p, float buf, float lr, float a)
+{
+    float g = grad + t.weight_decay * p;
+    if (t.h0 != 0.0f) {                                                  // momentum
+        buf = (t.flags & DCLL_OPT_FIRST) ? g : buf * t.h0 + a * g;      // (the update that creates the buffer: buf = g itself)
+        g = (t.flags & DCLL_OPT_NESTEROV) ? g + t.h0 * buf : buf;
+        t.s0[i] = buf;
+    }
+    t.param[i] = p - lr * g;
+}
+
+__device__ __forceinline__ void optim_update(const optim_args &a, int k, long i, float grad, float p, float x0, float x1, float x2)
+{
+    const dcll_optim_tensor &t = a.t[k];
+    const float d0 = a.dyn ? a.dyn[DCLL_OPTIM_DYN * k] : a.host[k][0], d1 = a.dyn ? a.dyn[DCLL_OPTIM_DYN * k + 1] : a.host[k][1];
+    const float d2 = a.dyn ? a.dyn[DCLL_OPTIM_DYN * k + 2] : a.host[k][2], d3 = a.dyn ? a.dyn[DCLL_OPTIM_DYN * k + 3] : a.host[k][3];
+    switch (t.kind) {                                                    // workgroup-uniform
+    case DCLL_OPT_ADAM: optim_adam(t, i, grad, p, x0, x1, x2, d0, d1, d2); break;
+    case DCLL_OPT_ADAMW: optim_adamw(t, i, grad, p, x0, x1, x2, d0, d1, d2, d3); break;
+    case DCLL_OPT_ADAMAX: optim_adamax(t, i, grad, p, x0, x1, d0, d1); break;
+    default: optim_sgd(t, i, grad, p, x0, d0, d1); break;
+    }
+}
+// parameter and state of element i of tensor k (a state the kind does not keep: 0)
+__device__ __forceinline__ void optim_load(const dcll_optim_tensor &t, long i, float &p, float &x0, float &x1, float &x2)
+{
+    p = t.param[i];
+    x0 = t.s0 ? t.s0[i] : 0.0f;
+    x1 = t.s1 ? t.s1[i] : 0.0f;
+    x2 = (t.s2 && (t.flags & DCLL_OPT_AMSGRAD)) ? t.s2[i] : 0.0f;
+}
+__device__ __forceinline__ void optim_element(const optim_args &a, int k, long i)
+{
+    float p, x0, x1, x2;
+    optim_load(a.t[k], i, p, x0, x1, x2);
+    optim_update(a, k, i, a.t[k].grad[i], p, x0, x1, x2);
+}
+
+__global__ __launch_bounds__(256) void k_optim_multi(optim_args a)
+{
+    int k = 0;
+    while (k + 1 < a.n_tensors && (long)blockIdx.x >= a.first[k + 1]) ++k;      // wave-uniform
+    const long i = ((long)blockIdx.x - a.first[k]) * 256 + threadIdx.x;
+    if (i >= a.t[k].n) return;
+    optim_element(a, k, i);
+}
+
+// tensors -> optim_args with `per_block` elements per workgroup (adam_fill's layout); every refusal of the struct array
+static int optim_fill(optim_args &a, const dcll_optim_tensor *tensors, int32_t n_tensors, const float *dyn, int per_block,
+                      const bool *skip, long *blocks_out, const char *who)
+{
+    if (!tensors || n_tensors < 0 || n_tensors > DCLL_OPTIM_MAX_TENSORS)
+        return fail(DCLL_ERR_INVALID, "bad argument (1..8 tensors)", who);
+    a.dyn = dyn;
+    long blocks = 0;
+    for (int k = 0; k < n_tensors; ++k) {
+        const dcll_optim_tensor &t = tensors[k];
+        if (!t.param || !t.grad || t.n < 0 || t.step < 1) return fail(DCLL_ERR_INVALID, "null tensor or step < 1", who);
+        const bool adam = t.kind == DCLL_OPT_ADAM || t.kind == DCLL_OPT_ADAMW;
+        if (!adam && t.kind != DCLL_OPT_ADAMAX && t.kind != DCLL_OPT_SGD) return fail(DCLL_ERR_INVALID, "unknown kind", who);
+        const int32_t allowed = adam ? DCLL_OPT_AMSGRAD
+                                     : (t.kind == DCLL_OPT_SGD && t.h0 != 0.0f) ? (DCLL_OPT_NESTEROV | DCLL_OPT_FIRST) : 0;
+        if (t.flags & ~allowed) return fail(DCLL_ERR_INVALID, "unknown flag bits for this kind", who);
+        const bool need0 = t.kind != DCLL_OPT_SGD || t.h0 != 0.0f, need1 = t.kind != DCLL_OPT_SGD;
+        if ((need0 && !t.s0) || (need1 && !t.s1) || ((t.flags & DCLL_OPT_AMSGRAD) && !t.s2))
+            return fail(DCLL_ERR_INVALID, "a state tensor of this kind is missing", who);
+        a.t[k] = t;
+        a.first[k] = blocks;
+        if (!(skip && skip[k])) blocks += (t.n + per_block - 1) / per_block;
+        float *h = a.host[k];
+        h[0] = t.lr;
+        h[1] = h[2] = h[3] = 0.0f;
+        if (t.kind == DCLL_OPT_SGD) {
+            h[1] = (float)(1.0 - (double)t.h1);
+        } else {
+            h[1] = (float)(1.0 / (1.0 - pow((double)t.h0, (double)t.step)));
+            if (adam) h[2] = (float)(1.0 / sqrt(1.0 - pow((double)t.h1, (double)t.step)));
+            if (t.kind == DCLL_OPT_ADAMW) h[3] = (float)(1.0 - (double)t.lr * (double)t.weight_decay);
+        }
+    }
+    a.first[n_tensors] = blocks;
+    a.n_tensors = n_tensors;
+    *blocks_out = blocks;
+    return DCLL_OK;
+}
+
+extern "C" int dcll_optim_step(const dcll_optim_tensor *tensors, int32_t n_tensors, const float *dyn, void *stream)
+{
+    if (n_tensors == 0) return DCLL_OK;
+    optim_args a;
+    long blocks = 0;
+    int rc = optim_fill(a, tensors, n_tensors, dyn, 256, nullptr, &blocks, "dcll_optim_step");
+    if (rc) return rc;
+    if (blocks == 0) return DCLL_OK;
+    if (blocks > 0x7fffffffL) return fail(DCLL_ERR_INVALID, "dcll_optim_step: too many elements");
+    hipLaunchKernelGGL(k_optim_multi, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    HIP_CHECK_LAUNCH("k_optim_multi");
+    return DCLL_OK;
+}
+
+struct reduce_optim_args {
+    optim_args a;
+    dcll_grad_parts L[DCLL_REDUCE_MAX_LAYERS];
+    long lfirst[DCLL_REDUCE_MAX_LAYERS + 1];
+    int groups[DCLL_REDUCE_MAX_LAYERS];
+    int n_layers;
+};
+
+// k_grad_reduce_adam's launch (same workgroups, same groups of partial rows, same order: the same dW / db) with optim_update
+__global__ __launch_bounds__(1024) void k_grad_reduce_optim(reduce_optim_args ra)
+{
+    __shared__ float red[16][64];
+    const long blk = blockIdx.x;
+    if (blk >= ra.lfirst[ra.n_layers]) {                        // plain elementwise workgroups: 1024 elements each
+        const long b2 = blk - ra.lfirst[ra.n_layers];
+        int k = 0;
+        while (k + 1 < ra.a.n_tensors && b2 >= ra.a.first[k + 1]) ++k;
+        const long i = (b2 - ra.a.first[k]) * 1024 + threadIdx.x;
+        if (i < ra.a.t[k].n) optim_element(ra.a, k, i);
+        return;
+    }
+    int l = 0;
+    while (l + 1 < ra.n_layers && blk >= ra.lfirst[l + 1]) ++l;     // wave-uniform
+    const dcll_grad_parts &P = ra.L[l];
+    const int GR = ra.groups[l];
+    const int lane = threadIdx.x & 63, grp = threadIdx.x >> 6;
+    const long i = (blk - ra.lfirst[l]) * 64 + lane;
+    const long total = (long)P.c_out * P.rowlen;
+    // parameter and state of the element this lane finishes: requested before the partial rows, as in k_grad_reduce_adam
+    const int co = (int)(i / P.rowlen);
+    const long n = i % P.rowlen;
+    const bool isw = n < P.rowlen - 1;
+    const int kt = isw ? P.adam_w : P.adam_b;
+    const long e = isw ? (long)co * (P.rowlen - 1) + n : co;
+    float p0 = 0.0f, x0 = 0.0f, x1 = 0.0f, x2 = 0.0f;
+    if (grp == 0 && i < total && kt >= 0) optim_load(ra.a.t[kt], e, p0, x0, x1, x2);
+    const float acc = partial_rows_sum(P, GR, grp, i, total);
+    red[grp][lane] = acc;
+    __syncthreads();
+    if (grp != 0 || i >= total) return;
+    float tot = red[0][lane];
+    for (int q = 1; q < GR; ++q) tot += red[q][lane];
+    if (isw) P.dW[e] = tot;
+    else if (P.db) P.db[co] = tot;
+    if (kt >= 0) optim_update(ra.a, kt, e, tot, p0, x0, x1, x2);
+}
+
+extern "C" int dcll_grad_reduce_optim(const dcll_grad_parts *layers, int32_t n_layers, const dcll_optim_tensor *tensors,
+                                      int32_t n_tensors, const float *dyn, void *stream)
+{
+    if (n_layers == 0 && n_tensors == 0) return DCLL_OK;
+    if (n_layers < 0 || n_layers > DCLL_REDUCE_MAX_LAYERS || (n_layers > 0 && !layers))
+        return fail(DCLL_ERR_INVALID, "dcll_grad_reduce_optim: bad argument (0..4 layers)");
+    if (n_tensors < 0 || n_tensors > DCLL_OPTIM_MAX_TENSORS || (n_tensors > 0 && !tensors))
+        return fail(DCLL_ERR_INVALID, "dcll_grad_reduce_optim: bad argument (0..8 tensors, non-NULL when n_tensors > 0)");
+    reduce_optim_args ra;
+    bool taken[DCLL_OPTIM_MAX_TENSORS] = {false};
+    long blocks = 0, ablocks = 0;
+    int rc = reduce_fill(layers, n_layers, tensors, n_tensors, taken, ra.L, ra.lfirst, ra.groups, &blocks, "dcll_grad_reduce_optim");
+    if (rc) return rc;
+    ra.n_layers = n_layers;
+    if (n_tensors > 0) {
+        rc = optim_fill(ra.a, tensors, n_tensors, dyn, 1024, taken, &ablocks, "dcll_grad_reduce_optim");
+        if (rc) return rc;
+    } else {
+        ra.a.n_tensors = 0;
+        ra.a.dyn = nullptr;
+        ra.a.first[0] = 0;
+    }
+    if (blocks + ablocks == 0) return DCLL_OK;
+    if (blocks + ablocks > 0x7fffffffL) return fail(DCLL_ERR_INVALID, "dcll_grad_reduce_optim: too many elements");
+    hipLaunchKernelGGL(k_grad_reduce_optim, dim3((unsigned)(blocks + ablocks)), dim3(1024), 0, (hipStream_t)stream, ra);
+    HIP_CHECK_LAUNCH("k_grad_reduce_optim");
     return DCLL_OK;
 }
 

@@ -1030,6 +1030,8 @@ class DCLLBase(nn.Module):
             self.optimizer = self._make_optimizer(optimizer, dclllayer.i2h.parameters(), dict(kwargs_optimizer))
             if self.dclllayer.output_layer:
                 self.optimizer2 = self._make_optimizer(optimizer, dclllayer.output_.parameters(), dict(lr=1e-4))
+        if os.environ.get('DCLL_NATIVE_OPTIM', '0') == '1':
+            self.native_optimizers = True
         self.burnin = burnin
         self.batch_size = batch_size
         self.collect_stats = collect_stats
@@ -1117,9 +1119,11 @@ class DCLLBase(nn.Module):
         backward and Adam as C-ABI calls — else None (then train_dcll builds the autograd graph around the same HIP
         forward / backward).  Served: Conv2dDCLLlayer; crit = SmoothL1Loss (beta 1) or MSELoss with mean reduction;
         optimizer(s) = torch.optim.Adam without amsgrad / maximize / capturable / fused; DCLL_NATIVE_LEARNING != 0.
+        With `native_optimizers` also SGD, Adamax, AdamW and amsgrad (_optimizer_served).
         A DenseDCLLlayer slice (with a bias) is served the same way (_learn_dense)."""
         cached = getattr(self, '_native_kind', _UNSET)      # (0 is a loss kind: SmoothL1Loss)
-        if cached is not _UNSET:
+        general = bool(self.native_optimizers)
+        if cached is not _UNSET and getattr(self, '_native_kind_general', False) == general:
             return cached
         kind = None
         crit, opt = getattr(self, 'crit', None), getattr(self, 'optimizer', None)
@@ -1141,15 +1145,40 @@ class DCLLBase(nn.Module):
         for o in opts:
             if kind is None:
                 break
-            if type(o) is not optim.Adam:
+            if not self._optimizer_served(o, general):
                 kind = None
-                break
-            for g in o.param_groups:
-                if g.get('amsgrad') or g.get('maximize') or g.get('capturable') or g.get('fused') or \
-                        g.get('differentiable') or isinstance(g['lr'], torch.Tensor):
-                    kind = None
-        self._native_kind = kind
+        self._native_kind, self._native_kind_general = kind, general
         return kind
+
+    # -- optimizers other than plain Adam on the native step (dcll_optim_step / dcll_grad_reduce_optim): opt-in -----------------
+    native_optimizers = False       # _native_learning also admits optim.SGD, optim.Adamax, optim.AdamW, and Adam / AdamW with
+                                    # amsgrad; DCLL_NATIVE_OPTIM=1 sets it at construction, ConvNetwork.native_optim_path per network
+    NATIVE_OPTIMIZERS = (optim.Adam, optim.AdamW, optim.Adamax, optim.SGD)
+
+    @staticmethod
+    def _optimizer_served(o, general):
+        """True if the native step applies this optimizer's update itself: torch.optim.Adam without amsgrad; with `general`
+        (native_optimizers) NATIVE_OPTIMIZERS, amsgrad included.  Never maximize / capturable / fused / differentiable or a
+        tensor-valued lr (with `general`: or weight_decay)."""
+        if type(o) is not optim.Adam and not (general and type(o) in DCLLBase.NATIVE_OPTIMIZERS):
+            return False
+        for g in o.param_groups:
+            if type(o) is optim.Adam and g.get('decoupled_weight_decay') and not general:
+                return False        # (AdamW's update under Adam's name: dcll_adam_step's decay is coupled; `general` routes it to OPT_ADAMW)
+            if (g.get('amsgrad') and not general) or g.get('maximize') or g.get('capturable') or g.get('fused') or \
+                    g.get('differentiable') or isinstance(g['lr'], torch.Tensor):
+                return False
+            if general and isinstance(g.get('weight_decay'), torch.Tensor):
+                return False
+        return True
+
+    def _optimizers(self):
+        return [self.optimizer] + ([self.optimizer2] if self.dclllayer.output_layer else [])
+
+    def _plain_adam(self):
+        """True if every optimizer of this slice is what dcll_adam_step serves: the slice keeps _adam_tensors and its calls"""
+        return all(type(o) is optim.Adam and not any(g.get('amsgrad') or g.get('decoupled_weight_decay') for g in o.param_groups)
+                   for o in self._optimizers())
 
     def _learn_forward_backward(self, input, target, want_loss=True, clout_out=None):
         """Forward of one step plus — once iter >= burnin (reference :691) — the gradients of the local loss(es) in the
@@ -1401,6 +1430,60 @@ class DCLLBase(nn.Module):
                                     eps=g['eps'], step=max(1, int(st['step']))))
         return out
 
+    def _optim_tensors(self, advance=True):
+        """_adam_tensors for every optimizer _optimizer_served admits, as dcll_optim_step entries (ops.optim_step's dicts), on the
+        state of the torch optimizer objects — created here, in torch's own layout, on first use (SGD with momentum:
+        momentum_buffer; Adamax: step, exp_avg, exp_inf; Adam / AdamW: step, exp_avg, exp_avg_sq and with amsgrad max_exp_avg_sq):
+        optimizer.state_dict() stays loadable by the torch class, `step` counts the updates.  A momentum buffer is created by the
+        call that counts its first update, which carries OPT_FIRST (torch: buf = clone(grad)); until then a call with
+        advance=False describes the tensor without a buffer (s0 None, OPT_FIRST: the library refuses to launch that)."""
+        from .._lib import OPT_AMSGRAD, OPT_NESTEROV, OPT_FIRST, OPT_ADAM, OPT_ADAMW, OPT_ADAMAX, OPT_SGD
+        out = []
+        zeros = lambda q: torch.zeros_like(q, memory_format=torch.preserve_format)
+        for opt in self._optimizers():
+            for g in opt.param_groups:
+                for q in g['params']:
+                    if q.grad is None:
+                        continue
+                    t = dict(param=q.data, grad=q.grad, s0=None, s1=None, s2=None, flags=0, lr=g['lr'],
+                             weight_decay=g['weight_decay'], eps=g.get('eps', 0.0), step=1)
+                    if type(opt) is optim.SGD:
+                        t.update(kind=OPT_SGD, h0=g['momentum'], h1=g['dampening'])
+                        if g['momentum'] != 0:              # (without momentum torch keeps no state entry: opt.state is not touched)
+                            st = opt.state.get(q, {})
+                            created = st.get('momentum_buffer') is None         # (torch's own mark of "no update yet": absent or None)
+                            if created and advance:
+                                opt.state[q]['momentum_buffer'] = zeros(q)
+                                st = opt.state[q]
+                            t['s0'] = st.get('momentum_buffer')
+                            t['flags'] = (OPT_NESTEROV if g['nesterov'] else 0) | (OPT_FIRST if created else 0)
+                    else:
+                        adamax = type(opt) is optim.Adamax
+                        second = 'exp_inf' if adamax else 'exp_avg_sq'
+                        ams = bool(g.get('amsgrad')) and not adamax
+                        st = opt.state[q]
+                        if len(st) == 0:
+                            st['step'] = torch.tensor(0.0)
+                            st['exp_avg'], st[second] = zeros(q), zeros(q)
+                            if ams:
+                                st['max_exp_avg_sq'] = zeros(q)
+                        if advance:
+                            st['step'] += 1
+                        decoupled = type(opt) is optim.AdamW or bool(g.get('decoupled_weight_decay'))
+                        t.update(kind=OPT_ADAMAX if adamax else OPT_ADAMW if decoupled else OPT_ADAM, h0=g['betas'][0],
+                                 h1=g['betas'][1], s0=st['exp_avg'], s1=st[second], s2=st['max_exp_avg_sq'] if ams else None,
+                                 flags=OPT_AMSGRAD if ams else 0, step=max(1, int(st['step'])))
+                    out.append(t)
+        return out
+
+    def _update_parameters(self):
+        """The optimizer step of this slice alone (train_dcll): dcll_adam_step, or dcll_optim_step where an optimizer is not plain
+        Adam"""
+        if self._plain_adam():
+            ops.adam_step(self._adam_tensors())
+        else:
+            ops.optim_step(self._optim_tensors())
+
     def train_dcll(self, input, target, do_train=True, regularize=0.05):
         """One local-learning step (reference :690-718): forward; after burn-in the local loss on pvoutput (+ the loss
         on the output_ logits for the output layer), its gradients through the HIP backward kernels, optimizer step(s).
@@ -1422,7 +1505,7 @@ class DCLLBase(nn.Module):
             if learned:
                 parallel.allreduce_mean_tensors(self._grad_tensors(), local_n=input.shape[0])
                 if do_train:
-                    ops.adam_step(self._adam_tensors())
+                    self._update_parameters()
                     self.dclllayer.weights_written()
             # (the loss value lives in a reused one-element device buffer: valid until the next step of this slice)
             return output, pvoutput, pv, pvmem, (loss.reshape(()) if learned else torch.Tensor([0]))

@@ -98,8 +98,9 @@ class ConvNetwork(torch.nn.Module):
                              'for THIS batch' % (x.shape[0], global_batch))
         if not all(s._native_learning() is not None for s in self.dcll_slices):
             spikes = x
-            for s in self.dcll_slices:
-                spikes, _, _, _, _ = s.train_dcll(spikes, labels, regularize=False)
+            with torch.enable_grad():          # (learn_sequence runs under no_grad: the autograd step raised there for every such optimizer)
+                for s in self.dcll_slices:
+                    spikes, _, _, _, _ = s.train_dcll(spikes, labels, regularize=False)
             return
         key = (tuple(x.shape), tuple(labels.shape))
         if key != self._learn_last_key:                # another geometry: the slices' buffers are reallocated
@@ -121,7 +122,7 @@ class ConvNetwork(torch.nn.Module):
             parallel.allreduce_slab_end(h)
         if learned:
             if ranks:
-                ops.adam_step([t for s in learned for t in s._adam_tensors()])
+                self._step_tensors(learned)
             else:
                 self._finish_learning(learned)
             for s in learned:
@@ -166,25 +167,51 @@ class ConvNetwork(torch.nn.Module):
         return learned, pending
 
     @staticmethod
+    def _general_optim(slices):
+        """True if some tensor of these slices is not plain Adam's (DCLLBase.native_optimizers admitted it): their update goes
+        through ops.optim_step / ops.grad_reduce_optim / ops.optim_dyn_values on DCLLBase._optim_tensors, OPTIM_DYN scalars per
+        tensor; else through today's Adam calls, 3 per tensor."""
+        return not all(s._plain_adam() for s in slices)
+
+    @staticmethod
+    def _step_tensors(slices, advance=True, dyn=None):
+        """The elementwise optimizer launch(es) over all tensors of `slices` (the rank-sharded step: the gradients are closed)"""
+        if ConvNetwork._general_optim(slices):
+            tensors = [t for s in slices for t in s._optim_tensors(advance=advance)]
+            # (a capture is taken after eager steps: the update that creates a momentum buffer is never replayed)
+            assert dyn is None or not any(t['flags'] & ops._lib.OPT_FIRST for t in tensors)
+            ops.optim_step(tensors, dyn=dyn)
+        else:
+            ops.adam_step([t for s in slices for t in s._adam_tensors(advance=advance)], dyn=dyn)
+
+    @staticmethod
     def _finish_learning(learned, advance=True, dyn=None):
         """Single rank: ONE launch reduces the open weight gradients of the slices that learned (fixed order: the gradients
         in .grad are bit-identical to the per-slice reduction) and applies torch.optim.Adam's update to all their tensors
-        (ops.grad_reduce_adam; output_.* get the plain elementwise update in the same launch)."""
+        (ops.grad_reduce_adam; output_.* get the plain elementwise update in the same launch).  Where a tensor is not plain
+        Adam's (_general_optim): ops.grad_reduce_optim, the same launch with the update chosen per tensor."""
         from .. import _lib
         tensors, layers, done = [], [], 0
+        general = ConvNetwork._general_optim(learned)
+        width, max_tensors = (_lib.OPTIM_DYN, _lib.OPTIM_MAX_TENSORS) if general else (3, _lib.ADAM_MAX_TENSORS)
 
         def flush():
             nonlocal tensors, layers, done
             if layers:
-                ops.grad_reduce_adam(layers, tensors, dyn=None if dyn is None else dyn[3 * done:3 * (done + len(tensors))])
+                d = None if dyn is None else dyn[width * done:width * (done + len(tensors))]
+                if general:
+                    assert dyn is None or not any(t['flags'] & _lib.OPT_FIRST for t in tensors)    # (captures follow eager steps)
+                    ops.grad_reduce_optim(layers, tensors, dyn=d)
+                else:
+                    ops.grad_reduce_adam(layers, tensors, dyn=d)
             done += len(tensors)
             tensors, layers = [], []
         # the ABI takes DCLL_REDUCE_MAX_LAYERS layers / DCLL_ADAM_MAX_TENSORS tensors per launch: the default three slices
         # are one launch, a deeper spec (radio_ml_conv_ref.yaml: 7 slices, 16 tensors) goes out in groups, slice order kept
-        # (dyn holds 3 floats per tensor in that same order)
+        # (dyn holds 3 floats per tensor in that same order; OPTIM_DYN with _general_optim)
         for s in learned:
-            mine = s._adam_tensors(advance=advance)
-            if len(layers) + 1 > _lib.REDUCE_MAX_LAYERS or len(tensors) + len(mine) > _lib.ADAM_MAX_TENSORS:
+            mine = s._optim_tensors(advance=advance) if general else s._adam_tensors(advance=advance)
+            if len(layers) + 1 > _lib.REDUCE_MAX_LAYERS or len(tensors) + len(mine) > max_tensors:
                 flush()
             parts = dict(s._learn_bufs['grads']['parts'])
             parts.update(adam_w=len(tensors), adam_b=len(tensors) + 1)     # (_adam_tensors: i2h.weight, i2h.bias first)
@@ -292,6 +319,7 @@ class ConvNetwork(torch.nn.Module):
         """Everything a captured step has baked in: addresses of state, parameters, gradients and optimizer state, and
         the hyper-parameters that are kernel arguments.  (lr and the step count are read on the device.)"""
         sig = []
+        general = self._general_optim(self.dcll_slices)
 
         def walk(d):
             for v in d.values():
@@ -314,9 +342,14 @@ class ConvNetwork(torch.nn.Module):
             sig.append(bool(L.i2h.slab_step_path))
             sig.append((bool(s.w3_learning_path), bool(L.i2h.w3_step_path), bool(s.w3_first_wgrad), bool(s.w3_dv)))
             sig.append(bool(s.pool_dv))
-            for t in s._adam_tensors(advance=False):
-                sig += [t['param'].data_ptr(), t['grad'].data_ptr(), t['exp_avg'].data_ptr(),
-                        t['exp_avg_sq'].data_ptr(), t['weight_decay'], t['beta1'], t['beta2'], t['eps']]
+            if not general:
+                for t in s._adam_tensors(advance=False):
+                    sig += [t['param'].data_ptr(), t['grad'].data_ptr(), t['exp_avg'].data_ptr(),
+                            t['exp_avg_sq'].data_ptr(), t['weight_decay'], t['beta1'], t['beta2'], t['eps']]
+                continue
+            for t in s._optim_tensors(advance=False):       # (lr, the step count and what follows from them are read on the device)
+                sig += [t['param'].data_ptr(), t['grad'].data_ptr()] + [None if t[k] is None else t[k].data_ptr() for k in ('s0', 's1', 's2')]
+                sig += [t['kind'], t['flags'], t['weight_decay'], t['h0'], t['h1'], t['eps']]
         return tuple(sig)
 
     @torch.no_grad()
@@ -340,14 +373,15 @@ class ConvNetwork(torch.nn.Module):
                 return False
         g['x'].copy_(x)
         g['y'].copy_(labels)
-        tensors = [t for s in self.dcll_slices for t in s._adam_tensors()]            # counts the update
+        general = self._general_optim(self.dcll_slices)
+        tensors = [t for s in self.dcll_slices for t in (s._optim_tensors() if general else s._adam_tensors())]    # counts the update
         slot = g['n'] % self._DYN_RING
         g['n'] += 1
         if g['events'][slot] is not None:
             g['events'][slot].synchronize()                     # the copy that last read this pinned row is done
         else:
             g['events'][slot] = torch.cuda.Event()
-        g['dyn_host_np'][slot, :] = ops.adam_dyn_values(tensors)
+        g['dyn_host_np'][slot, :] = ops.optim_dyn_values(tensors) if general else ops.adam_dyn_values(tensors)
         g['dyn'].copy_(g['dyn_host'][slot], non_blocking=True)
         g['events'][slot].record()
         if g['segments'] is None:
@@ -373,11 +407,13 @@ class ConvNetwork(torch.nn.Module):
 
     def _capture_learn(self, x, labels, sig):
         from ..dcll.pytorch_libdcll import DCLLClassification
-        n_t = sum(len(s._adam_tensors(advance=False)) for s in self.dcll_slices)
+        general = self._general_optim(self.dcll_slices)
+        n_t = sum(len(s._optim_tensors(advance=False) if general else s._adam_tensors(advance=False)) for s in self.dcll_slices)
+        n_dyn = (ops._lib.OPTIM_DYN if general else 3) * n_t
         dev = x.device
         g = dict(sig=sig, n=0, x=torch.empty_like(x), y=torch.empty_like(labels),
                  clout=torch.zeros((self.num_layers, x.shape[0]), device=dev, dtype=torch.int32),
-                 dyn=torch.zeros(3 * n_t, device=dev), dyn_host=torch.zeros((self._DYN_RING, 3 * n_t)).pin_memory(),
+                 dyn=torch.zeros(n_dyn, device=dev), dyn_host=torch.zeros((self._DYN_RING, n_dyn)).pin_memory(),
                  events=[None] * self._DYN_RING,
                  records=[isinstance(s, DCLLClassification) for s in self.dcll_slices])
         g['dyn_host_np'] = g['dyn_host'].numpy()
@@ -405,7 +441,7 @@ class ConvNetwork(torch.nn.Module):
                         assert l
                     pool = segments[i].pool() if pool is None else pool
                 with torch.cuda.graph(graph, pool=pool, capture_error_mode='thread_local'):
-                    ops.adam_step([t for s in self.dcll_slices for t in s._adam_tensors(advance=False)], dyn=g['dyn'])
+                    self._step_tensors(self.dcll_slices, advance=False, dyn=g['dyn'])
         finally:
             for s, it in zip(self.dcll_slices, iters):         # capturing records the launches, it runs nothing
                 s.iter = it
@@ -1197,6 +1233,29 @@ class ConvNetwork(torch.nn.Module):
             raise ops._lib.DCLLUnsupported('pool_dv_path cannot be combined with w3_step_path (w3_dv_path is its dv kernel)')
         for s in self.dcll_slices:              # (part of _graph_signature: a captured timestep of the other path is retaken)
             s.pool_dv = on
+
+    @property
+    def native_optim_path(self):
+        """True: the native learning step also serves slices whose optimizer is torch.optim.SGD, Adamax, AdamW, or Adam / AdamW with
+        amsgrad (DCLLBase.native_optimizers): their update is applied by k_grad_reduce_optim / k_optim_multi on the state tensors of
+        the torch optimizer objects, as torch's _single_tensor_* functions state it, instead of the whole step running under
+        autograd.  A network of plain Adam slices keeps its calls and its bits.  Combines with every learning, per-step and dv
+        path.  Default False (DCLL_NATIVE_OPTIM=1 sets it at construction); setting it True where a slice's optimizer is none of
+        DCLLBase.NATIVE_OPTIMIZERS, or uses maximize / capturable / fused / differentiable / a tensor lr or weight_decay, raises
+        DCLLUnsupported and leaves it as it was; switching it off is always allowed."""
+        return all(s.native_optimizers for s in self.dcll_slices)
+
+    @native_optim_path.setter
+    def native_optim_path(self, on):
+        on = bool(on)
+        if on:
+            for s in self.dcll_slices:
+                for o in ([getattr(s, 'optimizer', None)] + ([getattr(s, 'optimizer2', None)] if s.dclllayer.output_layer else [])):
+                    if o is None or not s._optimizer_served(o, True):
+                        raise ops._lib.DCLLUnsupported('native_optim_path: the optimizer of slice %s (%s) is not served'
+                                                       % (s.name, type(o).__name__))
+        for s in self.dcll_slices:              # (_native_learning looks at it again; _graph_signature follows the tensors' kinds)
+            s.native_optimizers = on
 
     # -- the fused path of any plain conv network (k_lif_seq_any, ABI 8): opt-in, beside test_sequence ---------------------
     def sequence_any_supported(self, wide=False, bands=None, tiles=None, slabs=None):

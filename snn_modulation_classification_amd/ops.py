@@ -1339,6 +1339,14 @@ def grad_reduce_adam(layers, tensors, dyn=None):
         raise ValueError("grad_reduce_adam: at most %d layers and %d tensors" % (_lib.REDUCE_MAX_LAYERS, _lib.ADAM_MAX_TENSORS))
     if dyn is not None:
         _expect(dyn, "dyn", torch.float32, numel=3 * len(tensors))
+    larr = _parts_array(layers, tensors, "grad_reduce_adam")
+    check(_lib.get().dcll_grad_reduce_adam(larr, len(layers), _adam_array(tensors), len(tensors), ptr(dyn), stream_ptr()),
+          "dcll_grad_reduce_adam")
+
+
+def _parts_array(layers, tensors, who):
+    """the dcll_grad_parts of grad_reduce_adam / grad_reduce_optim; a layer's 'adam_w' / 'adam_b' must name the tensor whose grad is
+    its dW / db"""
     larr = (_lib.GradParts * max(1, len(layers)))()
     for a, L in zip(larr, layers):
         _expect(L["dW"], "dW", torch.float32, numel=L["c_out"] * (L["rowlen"] - 1))
@@ -1348,9 +1356,76 @@ def grad_reduce_adam(layers, tensors, dyn=None):
         a.adam_w, a.adam_b = int(L.get("adam_w", -1)), int(L.get("adam_b", -1))
         for idx, key in ((a.adam_w, "dW"), (a.adam_b, "db")):
             if idx >= 0 and tensors[idx]["grad"].data_ptr() != L[key].data_ptr():
-                raise ValueError("grad_reduce_adam: tensors[%d]['grad'] is not the layer's %s" % (idx, key))
-    check(_lib.get().dcll_grad_reduce_adam(larr, len(layers), _adam_array(tensors), len(tensors), ptr(dyn), stream_ptr()),
-          "dcll_grad_reduce_adam")
+                raise ValueError("%s: tensors[%d]['grad'] is not the layer's %s" % (who, idx, key))
+    return larr
+
+
+OPT_KINDS = {"Adam": _lib.OPT_ADAM, "AdamW": _lib.OPT_ADAMW, "Adamax": _lib.OPT_ADAMAX, "SGD": _lib.OPT_SGD}
+
+
+def optim_dyn_values(tensors):
+    """Per tensor the DCLL_OPTIM_DYN step-dependent scalars of optim_step as a flat float list — (lr, 1 / bc1, 1 / sqrt(bc2), c) for
+    Adam / AdamW (c = 1 - lr * weight_decay, AdamW only), (lr, 1 / bc1, 0, 0) for Adamax, (lr, 1 - dampening, 0, 0) for SGD —
+    computed exactly as dcll_optim_step does on the host (float64 arithmetic on the float32 values of the struct)."""
+    f = lambda x: float(np.float32(x))
+    out = []
+    for t in tensors:
+        kind, h0, h1, step = int(t["kind"]), f(t["h0"]), f(t["h1"]), int(t["step"])
+        row = [float(t["lr"]), 0.0, 0.0, 0.0]
+        if kind == _lib.OPT_SGD:
+            row[1] = 1.0 - h1
+        else:
+            row[1] = 1.0 / (1.0 - math.pow(h0, step))
+            if kind in (_lib.OPT_ADAM, _lib.OPT_ADAMW):
+                row[2] = 1.0 / math.sqrt(1.0 - math.pow(h1, step))
+            if kind == _lib.OPT_ADAMW:
+                row[3] = 1.0 - f(t["lr"]) * f(t["weight_decay"])
+        out += row
+    return out
+
+
+def _optim_array(tensors, who="optim_step"):
+    arr = (_lib.OptimTensor * max(1, len(tensors)))()
+    for a, t in zip(arr, tensors):
+        prm = t["param"]
+        if not prm.is_cuda or not prm.is_contiguous():
+            raise _lib.DCLLHipError("%s: parameters must be contiguous device tensors" % who)
+        for key in ("param", "grad", "s0", "s1", "s2"):
+            if t.get(key) is not None:
+                _expect(t[key], key, torch.float32, numel=prm.numel())
+        a.param, a.grad = prm.data_ptr(), ptr(t["grad"]).value
+        a.s0, a.s1, a.s2 = (None if t.get(key) is None else ptr(t[key]).value for key in ("s0", "s1", "s2"))
+        a.n, a.step, a.kind, a.flags = prm.numel(), int(t["step"]), int(t["kind"]), int(t.get("flags", 0))
+        a.lr, a.weight_decay = float(t["lr"]), float(t["weight_decay"])
+        a.h0, a.h1, a.eps = float(t["h0"]), float(t["h1"]), float(t["eps"])
+    return arr
+
+
+def optim_step(tensors, dyn=None):
+    """adam_step for torch.optim.Adam / AdamW (with or without amsgrad), Adamax and SGD, mixed freely (dcll_optim_step, one launch
+    per OPTIM_MAX_TENSORS tensors).  tensors: dicts with param, grad (tensors), kind (OPT_KINDS), flags (OPT_AMSGRAD / OPT_NESTEROV /
+    OPT_FIRST), s0, s1, s2 (the state tensors of the kind, else None: exp_avg, exp_avg_sq, max_exp_avg_sq / exp_avg, exp_inf /
+    momentum_buffer), lr, weight_decay, h0, h1 (betas / momentum, dampening), eps, step (1-based count of this update).
+    dyn: optional device tensor (OPTIM_DYN floats per tensor, optim_dyn_values), read at execution time: the capturable form."""
+    lib = _lib.get()
+    if dyn is not None:
+        _expect(dyn, "dyn", torch.float32, numel=_lib.OPTIM_DYN * len(tensors))
+    for k0 in range(0, len(tensors), _lib.OPTIM_MAX_TENSORS):
+        part = tensors[k0:k0 + _lib.OPTIM_MAX_TENSORS]
+        d = None if dyn is None else dyn[_lib.OPTIM_DYN * k0:_lib.OPTIM_DYN * (k0 + len(part))]
+        check(lib.dcll_optim_step(_optim_array(part), len(part), ptr(d), stream_ptr()), "dcll_optim_step")
+
+
+def grad_reduce_optim(layers, tensors, dyn=None):
+    """grad_reduce_adam with optim_step's tensors (dcll_grad_reduce_optim): the layers' 'adam_w' / 'adam_b' index `tensors`; dW / db
+    are grad_reduce_adam's bits.  dyn as in optim_step."""
+    if len(layers) > _lib.REDUCE_MAX_LAYERS or len(tensors) > _lib.OPTIM_MAX_TENSORS:
+        raise ValueError("grad_reduce_optim: at most %d layers and %d tensors" % (_lib.REDUCE_MAX_LAYERS, _lib.OPTIM_MAX_TENSORS))
+    if dyn is not None:
+        _expect(dyn, "dyn", torch.float32, numel=_lib.OPTIM_DYN * len(tensors))
+    larr = _parts_array(layers, tensors, "grad_reduce_optim")
+    check(_lib.get().dcll_grad_reduce_optim(larr, len(layers), _optim_array(tensors, "grad_reduce_optim"), len(tensors), ptr(dyn),
+                                            stream_ptr()), "dcll_grad_reduce_optim")
 
 
 def cells_to_planes(cells, hw):

@@ -218,6 +218,16 @@ def parse_args(argv=None):
                         'it every gradient, is bit-identical.  Combines with every learning and step path except --w3_step_path '
                         '(which has --w3_dv_path); ignored with a notice there and where no layer of the network pools.  '
                         'Table: profiles/r28_pool_dv_timing.txt')
+    p.add_argument('--native_optim_path', action='store_true',
+                   help='opt in: with --optim_type Adamax or AdamW (through the layer API also SGD and amsgrad) the learning timestep '
+                        'stays on the native path — the update is applied by k_grad_reduce_optim in the launch that finishes the weight '
+                        'gradients, on the state tensors of the torch optimizer — instead of running under autograd with one '
+                        'optimizer.step() per slice.  Combines with every learning, step and dv path; ignored with a notice under '
+                        '--optim_type Adam (already native) and for optimizers that are not served (NAdam, RAdam, RMSprop).  '
+                        'Measured on an MI355X, radio_ml_conv.yaml on 16x16, five alternating fresh processes per arm, min-max '
+                        'net.learn ms per timestep, flag off -> on: Adamax 1.483-1.945 -> 0.208-0.211 at B = 64 (7.0-9.4x), 1.281-3.130 -> '
+                        '0.636-0.683 at B = 512 (1.9-4.9x); AdamW 1.399-1.781 -> 0.208-0.241 at B = 64 (5.8-8.6x), 1.537-1.791 -> '
+                        '0.635-0.640 at B = 512 (2.4-2.8x): faster at all four points.  Table: profiles/r29_optim_timing.txt')
     p.add_argument('--gpus', type=int, default=1, metavar='N',
                    help='ranks (one process per GPU): every batch is sharded over them, the local-learning gradients are '
                         'averaged over the ranks every timestep (one bucketed all-reduce)')
@@ -284,6 +294,7 @@ def main(argv=None):
     _opt_in_slab_learning(net, args)
     _opt_in_band_learning(net, args)
     _opt_in_pool_dv(net, args)
+    _opt_in_native_optim(net, args)
     parallel.freeze_startup_heap()          # (a full GC pass over the start-up heap costs ~100 ms inside the T-loop)
 
     if not args.no_save:
@@ -661,6 +672,26 @@ def _opt_in_pool_dv(net, args):
         net.pool_dv_path = True
 
 
+def _opt_in_native_optim(net, args):
+    """--native_optim_path: slices whose optimizer is SGD, Adamax, AdamW or uses amsgrad learn on the native step
+    (ConvNetwork.native_optim_path); runs behind the other opt-ins, whose paths it keeps."""
+    if not getattr(args, 'native_optim_path', False):
+        return
+    from snn_modulation_classification_amd._lib import DCLLUnsupported
+    if all(s._plain_adam() for s in net.dcll_slices):
+        print('--native_optim_path ignored: every optimizer of this network is plain Adam, which the native step serves already')
+        return
+    try:
+        net.native_optim_path = True
+    except DCLLUnsupported as e:
+        print('--native_optim_path ignored: %s' % e)
+        return
+    if not all(s._native_learning() is not None for s in net.dcll_slices):
+        net.native_optim_path = False
+        print('--native_optim_path ignored: the learning step of this network is not native whatever its optimizer (loss type, '
+              'layer options or DCLL_NATIVE_LEARNING=0 keep it under autograd)')
+
+
 def main_mnist(args):
     """--data MNIST (reference train.py:118-131): 28x28 images as frozen Poisson spike trains (image2spiketrain,
     gain 100), 10 classes, any conv spec that fits 28x28 (networks/mnist_conv.yaml), per-step protocol for learning
@@ -693,6 +724,7 @@ def main_mnist(args):
     _opt_in_slab_learning(net, args)
     _opt_in_band_learning(net, args)
     _opt_in_pool_dv(net, args)
+    _opt_in_native_optim(net, args)
     use_wide = _opt_in_wide_sequence(net, args, net.sequence_supported())      # (the condition of --any_sequence_path below)
     use_bands = _opt_in_band_sequence(net, args, net.sequence_supported())
     use_tiles = _opt_in_tile_sequence(net, args, net.sequence_supported())
