@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 import torch.optim as optim
 
-from .. import ops
+from .. import ops, paths
 from .._lib import DenseDesc
 
 logger = logging.getLogger(__name__)
@@ -282,26 +282,19 @@ class ContinuousConv2D(nn.Module):
                 rows.append(flat[:, 0])
         return torch.stack(rows).contiguous()
 
-    # _step: dcll_conv_lif_step_any (k_lif_step_any, ABI 10) instead of dcll_conv_lif_step; opt-in.  The supported switch is
-    # ConvNetwork.any_step_path, which asks step_any_supported() first; set here directly, a layer the library refuses (or one
-    # given int8 weights afterwards) raises DCLLUnsupported / ValueError from every step — there is no fall-back
-    any_step_path = False
-    # _step: dcll_conv_lif_step_w3 (k_lif_step_w3) instead; opt-in through ConvNetwork.w3_step_path, which asks
-    # w3_step_supported() first.  Set here directly the same holds: a layer the library refuses raises, there is no fall-back
-    w3_step_path = False
-    # _step: dcll_conv_lif_step_wide (k_lif_step_wide: layers of up to 64 output channels; c_out <= 32 runs k_lif_step_any)
-    # instead; opt-in through ConvNetwork.wide_step_path, which asks step_wide_supported() first.  Set here directly the same
-    # holds: a layer the library refuses raises, there is no fall-back
-    wide_step_path = False
-    # _step: dcll_conv_lif_step_slab (k_lif_step_slab: any number of output channels, bands of rows x slabs of 64 channels; a
-    # layer dcll_conv_lif_step_wide serves runs that call's kernels) instead; opt-in through ConvNetwork.slab_step_path, which
-    # asks step_slab_supported() first.  Set here directly the same holds: a layer the library refuses raises, no fall-back
-    slab_step_path = False
+    # _step: the layer call, one of paths.STEP_CALLS — None: dcll_conv_lif_step; 'any': dcll_conv_lif_step_any (k_lif_step_any, ABI 10);
+    # 'w3': dcll_conv_lif_step_w3 (k_lif_step_w3); 'wide': dcll_conv_lif_step_wide (k_lif_step_wide: up to 64 output channels; c_out <= 32
+    # runs k_lif_step_any); 'slab': dcll_conv_lif_step_slab (k_lif_step_slab: any number of output channels, bands of rows x slabs of
+    # 64 channels; a layer dcll_conv_lif_step_wide serves runs that call's kernels).  Opt-in.  The supported switches are ConvNetwork's
+    # (any_step_path, ...), which ask the path's predicate first; set here directly, a layer the library refuses (or one given int8
+    # weights afterwards) raises DCLLUnsupported / ValueError from every step — there is no fall-back.
+    step_path = None
+    # the boolean each path had before they became one state: views of step_path
+    any_step_path, w3_step_path, wide_step_path, slab_step_path = (paths.view('step_path', k) for k in ('any', 'w3', 'wide', 'slab'))
 
     def _step(self, input, pooling=(1, 1), i2o=None, output_=None, out=None, stacked=None, finish=None, want_v=True,
               defer_ro=False):
-        """Run one step through dcll_conv_lif_step (any_step_path: dcll_conv_lif_step_any; w3_step_path: dcll_conv_lif_step_w3); returns (s_pooled, p, o, pv_pooled,
-        v).  `out`: optional dict of reusable output buffers; `stacked` / `finish` / `defer_ro`: the fused readout tail of the
+        """Run one step through dcll_conv_lif_step, or step_path's call; returns (s_pooled, p, o, pv_pooled, v).  `out`: optional dict of reusable output buffers; `stacked` / `finish` / `defer_ro`: the fused readout tail of the
         step (ops.conv_lif_step)."""
         self._check_batch(input)
         desc = self.make_desc(input.shape[2:4], pooling, 0 if i2o is None else i2o.weight.shape[0],
@@ -314,9 +307,7 @@ class ContinuousConv2D(nn.Module):
                 st.eps0, st.eps1, arp,
                 None if i2o is None else i2o.weight, None if i2o is None else i2o.bias,
                 None if output_ is None else output_.weight, None if output_ is None else output_.bias, out=out,
-                q8=self.int8_weights(), stacked=stacked, finish=finish, want_v=want_v, defer_ro=defer_ro,
-                any_path=self.any_step_path, w3_path=self.w3_step_path, wide_path=self.wide_step_path,
-                slab_path=self.slab_step_path)
+                q8=self.int8_weights(), stacked=stacked, finish=finish, want_v=want_v, defer_ro=defer_ro, path=self.step_path)
 
     def _general(self):
         """True when the layer was built with an option outside the fused step (see _is_sigmoid)."""
@@ -697,45 +688,37 @@ class Conv2dDCLLlayer(nn.Module):
                                                lowhigh_iter0=lowhigh_iter0, q8=q8, presigmoid=presigmoid)
         return spk, pv, None
 
-    # -- the MFMA per-step forward of any plain conv layer (k_lif_step_any, ABI 10): opt-in through i2h.any_step_path --------
-    def step_any_supported(self):
-        """True if dcll_conv_lif_step_any serves this layer's steps: built inside the fused step (not _general()), fp32 weights
-        (no int8 form) and the library's own predicate (plain conv, c_out <= 32, kernel up to 16x16, the padded eps1 image and a
-        pooling layer's v plane within a workgroup's LDS — ops.step_any_supported)."""
+    # -- the opt-in per-step and learning paths (paths.PATHS): whether this layer is served ---------------------------------------------
+    def _served(self, predicates, *args, int8=False):
+        """True if the opt-in path whose ops predicate(s) are named serves this layer: built inside the fused step (not _general()),
+        fp32 weights (no int8 form) unless the path reads neither (`int8`: the weight gradients), and the library's own
+        predicate(s) on the layer's descriptor."""
         i = self.i2h
-        if i._general() or i.int8_weights() is not None:
+        if i._general() or (not int8 and i.int8_weights() is not None):
             return False
-        return ops.step_any_supported(i.make_desc(self.im_dims, self.pooling, self.target_size, self.output_layer))
+        desc = i.make_desc(self.im_dims, self.pooling, self.i2o.weight.shape[0], self.output_layer)
+        return all(getattr(ops, q)(desc, *args) for q in predicates.split())
 
-    # -- the MFMA per-step forward of the layers of up to 64 output channels (k_lif_step_wide): opt-in through i2h.wide_step_path
+    def step_any_supported(self):
+        """True if dcll_conv_lif_step_any serves this layer's steps (_served: plain conv, c_out <= 32, kernel up to 16x16, the padded
+        eps1 image and a pooling layer's v plane within a workgroup's LDS — ops.step_any_supported)."""
+        return self._served('step_any_supported')
+
     def step_wide_supported(self):
         """True if dcll_conv_lif_step_wide serves this layer's steps: as step_any_supported with up to 64 output channels
         (ops.step_wide_supported; c_out <= 32 runs k_lif_step_any)."""
-        i = self.i2h
-        if i._general() or i.int8_weights() is not None:
-            return False
-        return ops.step_wide_supported(i.make_desc(self.im_dims, self.pooling, self.target_size, self.output_layer))
+        return self._served('step_wide_supported')
 
-    # -- the MFMA per-step forward of layers of any number of output channels (k_lif_step_slab): opt-in through i2h.slab_step_path
     def step_slab_supported(self):
         """True if dcll_conv_lif_step_slab serves this layer's steps: as step_wide_supported with any number of output channels
         and any plane height whose band plan fits a workgroup's LDS (ops.step_slab_supported; a layer dcll_conv_lif_step_wide
         serves runs that call's kernels)."""
-        i = self.i2h
-        if i._general() or i.int8_weights() is not None:
-            return False
-        return ops.step_slab_supported(i.make_desc(self.im_dims, self.pooling, self.target_size, self.output_layer))
+        return self._served('step_slab_supported')
 
-    # -- the MFMA per-step forward and weight gradient of the (1,3) / 64-channel layers (k_lif_step_w3, k_bwd_wgrad_w3) ------
     def w3_step_supported(self):
-        """True if dcll_conv_lif_step_w3 and dcll_conv_lif_backward_w3 serve this layer: built inside the fused step (not
-        _general()), fp32 weights (no int8 form) and the library's predicates (c_in 1 or 64, c_out 64, kernel (1,3), padding
-        (0,1), pooling (1,2), w a power of two <= 256, h * w % 32 == 0 — ops.step_w3_supported / backward_w3_supported)."""
-        i = self.i2h
-        if i._general() or i.int8_weights() is not None:
-            return False
-        desc = i.make_desc(self.im_dims, self.pooling, self.target_size, self.output_layer)
-        return ops.step_w3_supported(desc) and ops.backward_w3_supported(desc)
+        """True if dcll_conv_lif_step_w3 and dcll_conv_lif_backward_w3 serve this layer (_served: c_in 1 or 64, c_out 64, kernel (1,3),
+        padding (0,1), pooling (1,2), w a power of two <= 256, h * w % 32 == 0 — ops.step_w3_supported / backward_w3_supported)."""
+        return self._served('step_w3_supported backward_w3_supported')
 
     # -- the fused path of any plain conv layer (k_lif_seq_any, ABI 8): opt-in, beside sequence_kind / forward_sequence ---
     def sequence_any_supported(self, wide=False, bands=None, tiles=None, slabs=None):
@@ -1247,83 +1230,71 @@ class DCLLBase(nn.Module):
             ops.dense_lif_backward(i2h.make_desc(L.i2o), i2h.state.eps1, pv, res[0], None, None, L.i2o.weight, out=gb)
         return s, p, pv, v, res[2], True
 
-    # -- the MFMA weight gradient of any plain conv layer (k_bwd_wgrad_any, ABI 9): opt-in, beside the default dispatch ------
-    any_learning_path = False       # _learn_tail: dcll_conv_lif_backward_any[_open] instead of dcll_conv_lif_backward[_open]
-
-    wide_learning_path = False      # _learn_tail: dcll_conv_lif_backward_wide[_open] (k_bwd_wgrad_wide: layers of up to 64 channels)
-
-    slab_learning_path = False      # _learn_tail: dcll_conv_lif_backward_slab[_open] (k_bwd_wgrad_slab: layers of any width, 64-channel slabs)
-
-    band_learning_path = False      # _learn_tail: dcll_conv_lif_backward_bands[_open] (k_bwd_wgrad_band: any plane height, a sample in bands
-                                    # of conv rows); True: the library's band rule, an int N: that many bands
-
-    w3_learning_path = False        # _learn_tail: dcll_conv_lif_backward_w3[_open] (k_bwd_wgrad_w3); set by ConvNetwork.w3_step_path
-    w3_first_wgrad = False          # with w3_learning_path: dcll_conv_lif_backward_w3f[_open] (the c_in 1 layer on k_bwd_wgrad_w3f);
+    # -- the opt-in paths of the learning step (paths.PATHS), beside the default dispatch ------------------------------------------------
+    # _learn_tail: the backward call, one of paths.BACKWARD_CALLS — None: dcll_conv_lif_backward[_open]; 'any': ..._any (k_bwd_wgrad_any,
+    # ABI 9); 'wide': ..._wide (k_bwd_wgrad_wide: layers of up to 64 channels); 'slab': ..._slab (k_bwd_wgrad_slab: layers of any width,
+    # 64-channel slabs); 'band': ..._bands (k_bwd_wgrad_band: any plane height, a sample in learning_bands bands of conv rows, 0: the
+    # library's band rule); 'w3': ..._w3 (k_bwd_wgrad_w3; set by ConvNetwork.w3_step_path)
+    learning_path = None
+    learning_bands = 0
+    # the attribute each path had before they became one state: views of learning_path (band_learning_path: False | True | N)
+    any_learning_path, wide_learning_path, slab_learning_path, w3_learning_path = (
+        paths.view('learning_path', k) for k in ('any', 'wide', 'slab', 'w3'))
+    band_learning_path = paths.band_view()
+    w3_first_wgrad = False          # with learning_path 'w3': dcll_conv_lif_backward_w3f[_open] (the c_in 1 layer on k_bwd_wgrad_w3f);
                                     # set by ConvNetwork.w3_first_wgrad
     pool_dv = False                 # _learn_tail: the backward call through dcll_conv_lif_backward_ex[_open] with DCLL_BWD_POOL_DV (the dv
                                     # plane of a pooling layer from k_bwd_dv_pool, bit-identical to k_bwd_dv's); set by ConvNetwork.pool_dv_path
-    w3_dv = False                   # with w3_learning_path: dcll_conv_lif_backward_w3_ex[_open] with DCLL_W3_DV (the dv plane from
+    w3_dv = False                   # with learning_path 'w3': dcll_conv_lif_backward_w3_ex[_open] with DCLL_W3_DV (the dv plane from
                                     # k_bwd_dv_w3, bit-identical to k_bwd_dv's); set by ConvNetwork.w3_dv_path
 
-    def w3_step_supported(self):
-        """True if this slice's layer steps and backward can run on k_lif_step_w3 / k_bwd_wgrad_w3
-        (Conv2dDCLLlayer.w3_step_supported)."""
+    def _band_count(self):
+        """The `bands` argument band_learning_path stands for: True -> 0 (the library's rule), an int N -> N."""
+        return self.learning_bands if self.learning_path == 'band' else 0
+
+    def _served(self, query, *args, **kw):
+        """True if this slice's layer is a Conv2dDCLLlayer that answers `query` (one of its *_supported methods, or the ops
+        predicate(s) of Conv2dDCLLlayer._served) with True"""
         L = self.dclllayer
-        return isinstance(L, Conv2dDCLLlayer) and L.w3_step_supported()
+        return isinstance(L, Conv2dDCLLlayer) and (getattr(L, query)() if hasattr(L, query) else L._served(query, *args, **kw))
+
+    def w3_step_supported(self):
+        """True if this slice's layer steps and backward can run on k_lif_step_w3 / k_bwd_wgrad_w3 (Conv2dDCLLlayer.w3_step_supported)."""
+        return self._served('w3_step_supported')
 
     def backward_any_supported(self):
         """True if this slice's native learning step can take its weight gradient from k_bwd_wgrad_any: a Conv2dDCLLlayer built
         inside the fused step (not _general()) that the library's predicate serves (plain conv, c_out <= 32, kernel up to 16x16,
         the smallest working set within a workgroup's LDS — ops.backward_any_supported)."""
-        L = self.dclllayer
-        if not isinstance(L, Conv2dDCLLlayer) or L.i2h._general():
-            return False
-        return ops.backward_any_supported(L.i2h.make_desc(L.im_dims, L.pooling, L.i2o.weight.shape[0], L.output_layer))
+        return self._served('backward_any_supported', int8=True)
 
     def backward_wide_supported(self):
         """True if this slice's native learning step can take its weight gradient from dcll_conv_lif_backward_wide: as
         backward_any_supported with up to 64 output channels (ops.backward_wide_supported; c_out <= 32 runs k_bwd_wgrad_any)."""
-        L = self.dclllayer
-        if not isinstance(L, Conv2dDCLLlayer) or L.i2h._general():
-            return False
-        return ops.backward_wide_supported(L.i2h.make_desc(L.im_dims, L.pooling, L.i2o.weight.shape[0], L.output_layer))
+        return self._served('backward_wide_supported', int8=True)
 
     def backward_slab_supported(self):
         """True if this slice's native learning step can take its weight gradient from dcll_conv_lif_backward_slab: as
         backward_wide_supported with any number of output channels (ops.backward_slab_supported; c_out <= 64 runs the wide path's
         kernels)."""
-        L = self.dclllayer
-        if not isinstance(L, Conv2dDCLLlayer) or L.i2h._general():
-            return False
-        return ops.backward_slab_supported(L.i2h.make_desc(L.im_dims, L.pooling, L.i2o.weight.shape[0], L.output_layer))
-
-    def _band_count(self):
-        """The `bands` argument band_learning_path stands for: True -> 0 (the library's rule), an int N -> N."""
-        v = self.band_learning_path
-        return 0 if v is True or v is False else int(v)
+        return self._served('backward_slab_supported', int8=True)
 
     def backward_bands_supported(self, bands=0):
         """True if this slice's native learning step can take its weight gradient from dcll_conv_lif_backward_bands with that band
         count (0: the library's rule): as backward_slab_supported on a plane of any height (ops.backward_bands_supported)."""
-        L = self.dclllayer
-        if not isinstance(L, Conv2dDCLLlayer) or L.i2h._general():
-            return False
-        return ops.backward_bands_supported(L.i2h.make_desc(L.im_dims, L.pooling, L.i2o.weight.shape[0], L.output_layer), bands)
+        return self._served('backward_bands_supported', bands, int8=True)
 
     def step_any_supported(self):
         """True if this slice's layer steps can run on k_lif_step_any (Conv2dDCLLlayer.step_any_supported)."""
-        L = self.dclllayer
-        return isinstance(L, Conv2dDCLLlayer) and L.step_any_supported()
+        return self._served('step_any_supported')
 
     def step_wide_supported(self):
         """True if this slice's layer steps can run on k_lif_step_wide (Conv2dDCLLlayer.step_wide_supported)."""
-        L = self.dclllayer
-        return isinstance(L, Conv2dDCLLlayer) and L.step_wide_supported()
+        return self._served('step_wide_supported')
 
     def step_slab_supported(self):
         """True if this slice's layer steps can run on k_lif_step_slab (Conv2dDCLLlayer.step_slab_supported)."""
-        L = self.dclllayer
-        return isinstance(L, Conv2dDCLLlayer) and L.step_slab_supported()
+        return self._served('step_slab_supported')
 
     def _backward_from_pv(self):
         """True if this slice's backward can take sigmoid' from pv: no pooling, <= 32 readout rows (k_bwd_dv_nopool)."""
@@ -1336,7 +1307,7 @@ class DCLLBase(nn.Module):
         dcll_conv_lif_backward into the parameters' .grad.  `open_reduce`: the weight gradient's last reduction is left to
         the caller's ops.grad_reduce_adam (self._learn_bufs['grads']['parts']); `defer_backward` (a list, with open_reduce): the
         backward is not launched here but appended for ops.conv_lif_backward_open_multi (all slices' dv in one launch) — with
-        any_learning_path, wide_learning_path, slab_learning_path, band_learning_path or w3_learning_path the slice's own open call is launched at once instead.
+        a learning_path the slice's own open call is launched at once instead.
         -> loss (1,) device tensor or None"""
         L = self.dclllayer
         i2h = L.i2h
@@ -1369,11 +1340,8 @@ class DCLLBase(nn.Module):
                 gb.update(d_outW=prm[2].grad, d_outb=prm[3].grad)
             ops.conv_lif_backward(desc, i2h.state.eps1, v, pv, g_p, g_o, None, None, L.i2o.weight,
                                   want_out=L.output_layer, out=gb, open_reduce=open_reduce,
-                                  defer=defer_backward if open_reduce else None, any_path=self.any_learning_path,
-                                  w3_path=self.w3_learning_path, w3_first=self.w3_first_wgrad, w3_dv=self.w3_dv,
-                                  wide_path=self.wide_learning_path, slab_path=self.slab_learning_path,
-                                  band_path=self.band_learning_path is not False, bands=self._band_count(),
-                                  pool_dv=self.pool_dv)
+                                  defer=defer_backward if open_reduce else None, path=self.learning_path,
+                                  bands=self._band_count(), w3_first=self.w3_first_wgrad, w3_dv=self.w3_dv, pool_dv=self.pool_dv)
         return loss
 
     def _grads_into_slab(self):

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 import yaml
 
-from .. import ops
+from .. import ops, paths
 from ..dcll import pytorch_libdcll as _libdcll
 from ..dcll.pytorch_libdcll import Conv2dDCLLlayer, DenseDCLLlayer, DCLLClassification  # noqa: F401
 
@@ -333,15 +333,7 @@ class ConvNetwork(torch.nn.Module):
             sig += [t.data_ptr() for t in (L.i2h.alpha, L.i2h.tau_m__dt, L.i2h.alphas, L.i2h.tau_s__dt, L.i2o.weight,
                                            L.i2o.bias)]
             walk(s.__dict__.get('_learn_bufs', {}))
-            sig.append(bool(s.any_learning_path))
-            sig.append(bool(s.wide_learning_path))
-            sig.append(bool(s.slab_learning_path))
-            sig.append((s.band_learning_path is not False, s._band_count()))
-            sig.append(bool(L.i2h.any_step_path))
-            sig.append(bool(L.i2h.wide_step_path))
-            sig.append(bool(L.i2h.slab_step_path))
-            sig.append((bool(s.w3_learning_path), bool(L.i2h.w3_step_path), bool(s.w3_first_wgrad), bool(s.w3_dv)))
-            sig.append(bool(s.pool_dv))
+            sig.append((s.learning_path, s._band_count(), L.i2h.step_path, bool(s.w3_first_wgrad), bool(s.w3_dv), bool(s.pool_dv)))
             if not general:
                 for t in s._adam_tensors(advance=False):
                     sig += [t['param'].data_ptr(), t['grad'].data_ptr(), t['exp_avg'].data_ptr(),
@@ -570,10 +562,7 @@ class ConvNetwork(torch.nn.Module):
                 sig += [L.output_.weight.data_ptr(), L.output_.bias.data_ptr()]
             q8 = L.i2h.int8_weights()            # (a capture taken on the int8 form must not outlive it)
             sig.append(None if q8 is None else (q8[0].data_ptr(), q8[1].data_ptr()))
-            sig.append(bool(L.i2h.any_step_path))
-            sig.append(bool(L.i2h.w3_step_path))
-            sig.append(bool(L.i2h.wide_step_path))
-            sig.append(bool(L.i2h.slab_step_path))
+            sig.append(L.i2h.step_path)
         return tuple(sig)
 
     @torch.no_grad()
@@ -626,37 +615,9 @@ class ConvNetwork(torch.nn.Module):
             self._opt_in_from_environment()
 
     def _opt_in_from_environment(self):
-        """DCLL_ANY_STEP_PATH=1 in the environment = `net.any_step_path = True` at the network's first reset(True), for the entry
-        points without a flag of their own (test_radio_ml.py: `DCLL_ANY_STEP_PATH=1 python test_radio_ml.py --no_sequence_path`
-        runs its per-step loop on k_lif_step_any).  Ignored with a notice where a layer is not served; unset or 0: nothing
-        changes.  Looked at once per network, so a later `net.any_step_path = False` holds.
-        DCLL_WIDE_STEP_PATH=1 = `net.wide_step_path = True` (k_lif_step_wide: layers of up to 64 output channels) by the same
-        rule; together with DCLL_ANY_STEP_PATH=1 the latter wins where it is served and this one is ignored with a notice.
-        DCLL_SLAB_STEP_PATH=1 = `net.slab_step_path = True` (k_lif_step_slab: any number of output channels) by the same rule;
-        ignored with a notice where a layer is not served or another per-step path is already on."""
-        if not (self.__dict__.get('_any_step_env_seen') or os.environ.get('DCLL_ANY_STEP_PATH', '0') in ('', '0')):
-            self.__dict__['_any_step_env_seen'] = True
-            if self.step_any_supported():
-                self.any_step_path = True
-            else:
-                print('DCLL_ANY_STEP_PATH ignored: k_lif_step_any does not serve every layer of this network')
-        if not (self.__dict__.get('_wide_step_env_seen') or os.environ.get('DCLL_WIDE_STEP_PATH', '0') in ('', '0')):
-            self.__dict__['_wide_step_env_seen'] = True
-            if not self.step_wide_supported():
-                print('DCLL_WIDE_STEP_PATH ignored: k_lif_step_wide does not serve every layer of this network')
-            elif self.w3_step_path or any(s.dclllayer.i2h.any_step_path for s in self.dcll_slices):
-                print('DCLL_WIDE_STEP_PATH ignored: another per-step path (any_step_path / w3_step_path) is on')
-            else:
-                self.wide_step_path = True
-        if not (self.__dict__.get('_slab_step_env_seen') or os.environ.get('DCLL_SLAB_STEP_PATH', '0') in ('', '0')):
-            self.__dict__['_slab_step_env_seen'] = True
-            if not self.step_slab_supported():
-                print('DCLL_SLAB_STEP_PATH ignored: k_lif_step_slab does not serve every layer of this network')
-            elif self.w3_step_path or any(s.dclllayer.i2h.any_step_path or s.dclllayer.i2h.wide_step_path
-                                          for s in self.dcll_slices):
-                print('DCLL_SLAB_STEP_PATH ignored: another per-step path (any_step_path / wide_step_path / w3_step_path) is on')
-            else:
-                self.slab_step_path = True
+        """The switches with an environment variable (DCLL_ANY_STEP_PATH, DCLL_WIDE_STEP_PATH, DCLL_SLAB_STEP_PATH = 1: see their
+        properties), looked at once per network: paths.from_environment."""
+        paths.from_environment(self)
 
     def write_stats(self, writer, epoch, comment=''):
         for s in self.dcll_slices:
@@ -927,335 +888,52 @@ class ConvNetwork(torch.nn.Module):
             res['o'] = res['o'].clone()
         return res
 
-    # -- the MFMA weight gradient of any plain conv layer (k_bwd_wgrad_any, ABI 9): opt-in, beside the default dispatch ------
+    # -- the opt-in per-step and learning paths, beside the default dispatch: one property per entry of paths.PATHS (its `doc`), made
+    # below the class; what excludes what, and the order of the checks, is paths.refusal ------------------------------------------
+    def _all_served(self, query, *args):
+        return all(getattr(s, query)(*args) for s in self.dcll_slices)
+
     def backward_any_supported(self):
         """True if every slice is served by dcll_conv_lif_backward_any (DCLLBase.backward_any_supported)."""
-        return all(s.backward_any_supported() for s in self.dcll_slices)
+        return self._all_served('backward_any_supported')
 
-    @property
-    def any_learning_path(self):
-        """True: every slice's learning step takes its weight gradient from k_bwd_wgrad_any (fp32 MFMA, any plain conv layer with
-        c_out <= 32 and a kernel up to 16x16 — also layers above 64 taps, which the default path refuses) instead of the
-        default dispatch.  The step's structure is unchanged: layer kernels, tails, one dcll_grad_reduce_adam.  Default False;
-        setting it on a network that is not fully served raises DCLLUnsupported."""
-        return all(s.any_learning_path for s in self.dcll_slices)
-
-    @any_learning_path.setter
-    def any_learning_path(self, on):
-        on = bool(on)
-        if on and self.w3_step_path:
-            raise ops._lib.DCLLUnsupported('any_learning_path cannot be combined with w3_step_path')
-        if on and any(s.wide_learning_path for s in self.dcll_slices):
-            raise ops._lib.DCLLUnsupported('any_learning_path cannot be combined with wide_learning_path')
-        if on and any(s.slab_learning_path for s in self.dcll_slices):
-            raise ops._lib.DCLLUnsupported('any_learning_path cannot be combined with slab_learning_path')
-        if on and any(s.band_learning_path is not False for s in self.dcll_slices):
-            raise ops._lib.DCLLUnsupported('any_learning_path cannot be combined with band_learning_path')
-        if on and not self.backward_any_supported():
-            raise ops._lib.DCLLUnsupported('dcll_conv_lif_backward_any does not serve every layer of this network')
-        for s in self.dcll_slices:
-            s.any_learning_path = on            # (part of _graph_signature: a captured timestep of the other path is retaken)
-
-    # -- the MFMA weight gradient of layers with up to 64 output channels (k_bwd_wgrad_wide): opt-in, beside the default dispatch --
     def backward_wide_supported(self):
         """True if every slice is served by dcll_conv_lif_backward_wide (DCLLBase.backward_wide_supported)."""
-        return all(s.backward_wide_supported() for s in self.dcll_slices)
+        return self._all_served('backward_wide_supported')
 
-    @property
-    def wide_learning_path(self):
-        """True: every slice's learning step takes its weight gradient from dcll_conv_lif_backward_wide — k_bwd_wgrad_wide (fp32
-        MFMA, two 32-row M tiles) for the layers of 33 .. 64 output channels that a netscale above 1 makes, k_bwd_wgrad_any for
-        the narrower ones — instead of the default dispatch.  The step's structure is unchanged: layer kernels, tails, one
-        dcll_grad_reduce_adam.  Default False; setting it on a network that is not fully served, or together with w3_step_path or
-        any_learning_path, raises DCLLUnsupported and leaves it off; switching it off is always allowed."""
-        return all(s.wide_learning_path for s in self.dcll_slices)
-
-    @wide_learning_path.setter
-    def wide_learning_path(self, on):
-        on = bool(on)
-        if on and (self.w3_step_path or any(s.any_learning_path for s in self.dcll_slices)):
-            raise ops._lib.DCLLUnsupported('wide_learning_path cannot be combined with w3_step_path / any_learning_path')
-        if on and any(s.slab_learning_path for s in self.dcll_slices):
-            raise ops._lib.DCLLUnsupported('wide_learning_path cannot be combined with slab_learning_path')
-        if on and any(s.band_learning_path is not False for s in self.dcll_slices):
-            raise ops._lib.DCLLUnsupported('wide_learning_path cannot be combined with band_learning_path')
-        if on and not self.backward_wide_supported():
-            raise ops._lib.DCLLUnsupported('dcll_conv_lif_backward_wide does not serve every layer of this network')
-        for s in self.dcll_slices:
-            s.wide_learning_path = on           # (part of _graph_signature: a captured timestep of the other path is retaken)
-
-    # -- the MFMA weight gradient of layers of ANY width, in slabs of 64 output channels (k_bwd_wgrad_slab): opt-in, beside the others --
     def backward_slab_supported(self):
         """True if every slice is served by dcll_conv_lif_backward_slab (DCLLBase.backward_slab_supported)."""
-        return all(s.backward_slab_supported() for s in self.dcll_slices)
+        return self._all_served('backward_slab_supported')
 
-    @property
-    def slab_learning_path(self):
-        """True: every slice's learning step takes its weight gradient from dcll_conv_lif_backward_slab — k_bwd_wgrad_slab (fp32
-        MFMA, one slab of 64 output channels per workgroup) for the layers of more than 64 output channels that a netscale above
-        2 makes, k_bwd_wgrad_wide / k_bwd_wgrad_any for the narrower ones — instead of the default dispatch.  The step's structure
-        is unchanged: layer kernels, tails, one dcll_grad_reduce_adam.  Default False; setting it on a network that is not fully
-        served, or together with w3_step_path, any_learning_path or wide_learning_path, raises DCLLUnsupported and leaves it off;
-        switching it off is always allowed."""
-        return all(s.slab_learning_path for s in self.dcll_slices)
-
-    @slab_learning_path.setter
-    def slab_learning_path(self, on):
-        on = bool(on)
-        if on and (self.w3_step_path or any(s.any_learning_path or s.wide_learning_path or s.w3_learning_path for s in self.dcll_slices)):
-            raise ops._lib.DCLLUnsupported('slab_learning_path cannot be combined with w3_step_path / any_learning_path / '
-                                           'wide_learning_path')
-        if on and any(s.band_learning_path is not False for s in self.dcll_slices):
-            raise ops._lib.DCLLUnsupported('slab_learning_path cannot be combined with band_learning_path')
-        if on and not self.backward_slab_supported():
-            raise ops._lib.DCLLUnsupported('dcll_conv_lif_backward_slab does not serve every layer of this network')
-        for s in self.dcll_slices:
-            s.slab_learning_path = on           # (part of _graph_signature: a captured timestep of the other path is retaken)
-
-    # -- the MFMA weight gradient on planes of ANY height, a sample in bands of conv rows (k_bwd_wgrad_band): opt-in, beside the others --
     def backward_bands_supported(self, bands=0):
         """True if every slice is served by dcll_conv_lif_backward_bands with that band count (0: the library's rule;
         DCLLBase.backward_bands_supported)."""
-        return all(s.backward_bands_supported(bands) for s in self.dcll_slices)
+        return self._all_served('backward_bands_supported', bands)
 
-    @property
-    def band_learning_path(self):
-        """False, True or an int N.  True: every slice's learning step takes its weight gradient from dcll_conv_lif_backward_bands —
-        k_bwd_wgrad_band (fp32 MFMA, a sample cut into bands of conv-output rows: LDS does not grow with the plane height) for the
-        layers whose sample the slab path cannot stage, dcll_conv_lif_backward_slab's kernels for the layers that call serves —
-        instead of the default dispatch.  An int N >= 2: exactly N bands per sample in every slice (1: the slab call itself).  The
-        step's structure is unchanged: layer kernels, tails, one dcll_grad_reduce_adam.  Default False; setting it on a network with
-        a slice that is not served, or together with w3_step_path, any_learning_path, wide_learning_path or slab_learning_path,
-        raises DCLLUnsupported and leaves it off; switching it off is always allowed.  Combines with any_step_path, wide_step_path
-        and slab_step_path."""
-        vals = [s.band_learning_path for s in self.dcll_slices]
-        return vals[0] if vals and all(v is not False and v == vals[0] and type(v) is type(vals[0]) for v in vals) else False
-
-    @band_learning_path.setter
-    def band_learning_path(self, on):
-        if on is None or on is False:
-            on = False
-        elif on is not True:
-            on = int(on)
-            if on < 0:
-                raise ops._lib.DCLLUnsupported('band_learning_path: a band count is >= 0')
-            if on == 0:
-                on = True                       # (0 bands: the library's rule)
-        if on is not False and (self.w3_step_path or any(s.any_learning_path or s.wide_learning_path or s.slab_learning_path or
-                                                         s.w3_learning_path for s in self.dcll_slices)):
-            raise ops._lib.DCLLUnsupported('band_learning_path cannot be combined with w3_step_path / any_learning_path / '
-                                           'wide_learning_path / slab_learning_path')
-        if on is not False and not self.backward_bands_supported(0 if on is True else on):
-            raise ops._lib.DCLLUnsupported('dcll_conv_lif_backward_bands does not serve every layer of this network')
-        for s in self.dcll_slices:
-            s.band_learning_path = on           # (part of _graph_signature: a captured timestep of the other path is retaken)
-
-    # -- the MFMA per-step forward of any plain conv layer (k_lif_step_any, ABI 10): opt-in, beside the default dispatch -------
     def step_any_supported(self):
         """True if every layer's steps are served by dcll_conv_lif_step_any (Conv2dDCLLlayer.step_any_supported)."""
-        return all(s.step_any_supported() for s in self.dcll_slices)
+        return self._all_served('step_any_supported')
 
-    @property
-    def any_step_path(self):
-        """True: every per-step layer call — net.test(x[t]), every learning timestep, Conv2dDCLLlayer.forward, the autograd
-        nodes — runs k_lif_step_any (one fp32-MFMA launch with the traces and the pooling fused in; any plain conv layer with
-        c_out <= 32 and a kernel up to 16x16) instead of dcll_conv_lif_step's dispatch.  The readout tails and the sequence
-        calls (test_sequence, test_sequence_any) are untouched.  Default False; setting it on a network that is not fully
-        served (c_out 64, int8 weights) raises DCLLUnsupported."""
-        return all(s.dclllayer.i2h.any_step_path for s in self.dcll_slices)
-
-    @any_step_path.setter
-    def any_step_path(self, on):
-        on = bool(on)
-        if on and self.w3_step_path:
-            raise ops._lib.DCLLUnsupported('any_step_path cannot be combined with w3_step_path')
-        if on and any(s.dclllayer.i2h.wide_step_path for s in self.dcll_slices):
-            raise ops._lib.DCLLUnsupported('any_step_path cannot be combined with wide_step_path')
-        if on and any(s.dclllayer.i2h.slab_step_path for s in self.dcll_slices):
-            raise ops._lib.DCLLUnsupported('any_step_path cannot be combined with slab_step_path')
-        if on and not self.step_any_supported():
-            raise ops._lib.DCLLUnsupported('dcll_conv_lif_step_any does not serve every layer of this network')
-        for s in self.dcll_slices:
-            s.dclllayer.i2h.any_step_path = on  # (part of _graph_signature and _test_signature: a capture of the other path is retaken)
-
-    # -- the MFMA per-step forward of layers with up to 64 output channels (k_lif_step_wide): opt-in, beside the default dispatch --
     def step_wide_supported(self):
         """True if every layer's steps are served by dcll_conv_lif_step_wide (Conv2dDCLLlayer.step_wide_supported)."""
-        return all(s.step_wide_supported() for s in self.dcll_slices)
+        return self._all_served('step_wide_supported')
 
-    @property
-    def wide_step_path(self):
-        """True: every per-step layer call — net.test(x[t]), every learning timestep, Conv2dDCLLlayer.forward, the autograd
-        nodes — runs dcll_conv_lif_step_wide: k_lif_step_wide (k_lif_step_any's form with two 32-row M tiles) for the layers of
-        33 .. 64 output channels that a netscale above 1 makes, k_lif_step_any for the narrower ones, instead of
-        dcll_conv_lif_step's dispatch.  The readout tails and the sequence calls are untouched; combines with
-        wide_learning_path, any_learning_path and the default learning path.  Default False; setting it on a network that is
-        not fully served (c_out above 64, int8 weights), or together with any_step_path or w3_step_path, raises DCLLUnsupported
-        and leaves it off; switching it off is always allowed."""
-        return all(s.dclllayer.i2h.wide_step_path for s in self.dcll_slices)
-
-    @wide_step_path.setter
-    def wide_step_path(self, on):
-        on = bool(on)
-        if on and (self.w3_step_path or any(s.dclllayer.i2h.any_step_path for s in self.dcll_slices)):
-            raise ops._lib.DCLLUnsupported('wide_step_path cannot be combined with any_step_path / w3_step_path')
-        if on and any(s.dclllayer.i2h.slab_step_path for s in self.dcll_slices):
-            raise ops._lib.DCLLUnsupported('wide_step_path cannot be combined with slab_step_path')
-        if on and not self.step_wide_supported():
-            raise ops._lib.DCLLUnsupported('dcll_conv_lif_step_wide does not serve every layer of this network')
-        for s in self.dcll_slices:
-            s.dclllayer.i2h.wide_step_path = on # (part of _graph_signature and _test_signature: a capture of the other path is retaken)
-
-    # -- the MFMA per-step forward of layers of any number of output channels (k_lif_step_slab): opt-in, beside the default dispatch
     def step_slab_supported(self):
         """True if every layer's steps are served by dcll_conv_lif_step_slab (Conv2dDCLLlayer.step_slab_supported)."""
-        return all(s.step_slab_supported() for s in self.dcll_slices)
+        return self._all_served('step_slab_supported')
 
-    @property
-    def slab_step_path(self):
-        """True: every per-step layer call — net.test(x[t]), every learning timestep, Conv2dDCLLlayer.forward, the autograd
-        nodes — runs dcll_conv_lif_step_slab: k_lif_step_slab (k_lif_step_wide's chains over B x bands of rows x slabs of 64
-        output channels) for the layers of more than 64 output channels that a netscale above 2 makes and for the planes whose
-        padded eps1 image exceeds a workgroup's LDS, dcll_conv_lif_step_wide's kernels for the layers that call serves, instead
-        of dcll_conv_lif_step's dispatch.  The readout tails and the sequence calls are untouched; combines with
-        slab_learning_path, wide_learning_path, any_learning_path and the default learning path.  Default False; setting it on a
-        network that is not fully served (int8 weights, general-option layers, a plane of which not one pooled row fits), or
-        together with any_step_path, wide_step_path or w3_step_path, raises DCLLUnsupported and leaves it off; switching it off
-        is always allowed."""
-        return all(s.dclllayer.i2h.slab_step_path for s in self.dcll_slices)
-
-    @slab_step_path.setter
-    def slab_step_path(self, on):
-        on = bool(on)
-        if on and (self.w3_step_path or any(s.dclllayer.i2h.any_step_path or s.dclllayer.i2h.wide_step_path
-                                            for s in self.dcll_slices)):
-            raise ops._lib.DCLLUnsupported('slab_step_path cannot be combined with any_step_path / wide_step_path / w3_step_path')
-        if on and not self.step_slab_supported():
-            raise ops._lib.DCLLUnsupported('dcll_conv_lif_step_slab does not serve every layer of this network')
-        for s in self.dcll_slices:
-            s.dclllayer.i2h.slab_step_path = on # (part of _graph_signature and _test_signature: a capture of the other path is retaken)
-
-    # -- the MFMA learning step of the (1,3) / 64-channel layers of radio_ml_conv_ref.yaml: opt-in, beside the default dispatch --
     def w3_step_supported(self):
         """True if every layer's steps and backward are served by dcll_conv_lif_step_w3 / dcll_conv_lif_backward_w3
         (Conv2dDCLLlayer.w3_step_supported): radio_ml_conv_ref.yaml at netscale 1 with fp32 weights, on planes whose width is a
         power of two <= 256 and stays >= 2 through the poolings."""
-        return all(s.w3_step_supported() for s in self.dcll_slices)
+        return self._all_served('w3_step_supported')
 
-    @property
-    def w3_step_path(self):
-        """True: every per-step layer call — net.test(x[t]), every learning timestep, Conv2dDCLLlayer.forward — runs
-        k_lif_step_w3 (traces, fp32-MFMA chains and the (1,2) pooling in one launch) instead of dcll_conv_lif_step's k_trace +
-        k_conv_lif_tiled<1,3> + k_pool, and every learning step takes the weight gradient of its 64 -> 64 layers from
-        k_bwd_wgrad_w3 instead of k_bwd_wgrad.  One switch for both halves.  The readout tails and the sequence calls
-        (test_sequence, the burn-in of learn_sequence) are untouched.  Default False; setting it on a network with a layer that
-        is not served (other geometry, int8 weights, netscale != 1, general-option layers) or together with any_step_path /
-        any_learning_path raises DCLLUnsupported and leaves it off; switching it off is always allowed."""
-        return all(s.w3_learning_path and s.dclllayer.i2h.w3_step_path for s in self.dcll_slices)
-
-    @w3_step_path.setter
-    def w3_step_path(self, on):
-        on = bool(on)
-        if on and (any(s.any_learning_path for s in self.dcll_slices) or
-                   any(s.dclllayer.i2h.any_step_path for s in self.dcll_slices)):
-            raise ops._lib.DCLLUnsupported('w3_step_path cannot be combined with any_step_path / any_learning_path')
-        if on and any(s.wide_learning_path for s in self.dcll_slices):
-            raise ops._lib.DCLLUnsupported('w3_step_path cannot be combined with wide_learning_path')
-        if on and any(s.slab_learning_path for s in self.dcll_slices):
-            raise ops._lib.DCLLUnsupported('w3_step_path cannot be combined with slab_learning_path')
-        if on and any(s.band_learning_path is not False for s in self.dcll_slices):
-            raise ops._lib.DCLLUnsupported('w3_step_path cannot be combined with band_learning_path')
-        if on and any(s.dclllayer.i2h.wide_step_path for s in self.dcll_slices):
-            raise ops._lib.DCLLUnsupported('w3_step_path cannot be combined with wide_step_path')
-        if on and any(s.dclllayer.i2h.slab_step_path for s in self.dcll_slices):
-            raise ops._lib.DCLLUnsupported('w3_step_path cannot be combined with slab_step_path')
-        if on and any(s.pool_dv for s in self.dcll_slices):
-            raise ops._lib.DCLLUnsupported('w3_step_path cannot be combined with pool_dv_path (w3_dv_path is its dv kernel)')
-        if on and not self.w3_step_supported():
-            raise ops._lib.DCLLUnsupported('dcll_conv_lif_step_w3 / dcll_conv_lif_backward_w3 do not serve every layer of this '
-                                           'network')
-        for s in self.dcll_slices:              # (part of _graph_signature and _test_signature: a capture of the other path is retaken)
-            s.w3_learning_path = on
-            s.dclllayer.i2h.w3_step_path = on
-            if not on:
-                s.w3_first_wgrad = False        # (it rides on the w3 path)
-                s.w3_dv = False                 # (likewise)
-
-    @property
-    def w3_first_wgrad(self):
-        """True: with w3_step_path, the first layer (c_in 1 -> 64) takes its weight gradient from k_bwd_wgrad_w3f (a register-only
-        streaming reduction of the dv plane; dcll_conv_lif_backward_w3f[_open]) instead of the generic k_bwd_wgrad; the 64 -> 64
-        layers and everything else are w3_step_path's.  That layer's dW / db are then summed in another order (not bit-identical,
-        inside the weight-gradient tolerance).  Default False; setting it True while w3_step_path is off raises DCLLUnsupported
-        and leaves it off; w3_step_path = False clears it; switching it off is always allowed."""
-        return all(s.w3_first_wgrad for s in self.dcll_slices)
-
-    @w3_first_wgrad.setter
-    def w3_first_wgrad(self, on):
-        on = bool(on)
-        if on and not self.w3_step_path:
-            raise ops._lib.DCLLUnsupported('w3_first_wgrad needs w3_step_path (set it first)')
-        for s in self.dcll_slices:              # (part of _graph_signature: a captured timestep of the other path is retaken)
-            s.w3_first_wgrad = on
-
-    @property
-    def w3_dv_path(self):
-        """True: with w3_step_path, every layer's backward takes its dv plane from k_bwd_dv_w3 (a streaming form of k_bwd_dv for
-        the (1,2) pooling of these layers; dcll_conv_lif_backward_w3_ex[_open] with DCLL_W3_DV) instead of the generic k_bwd_dv.
-        The plane is bit-identical, so spikes, state, every gradient and the parameters after Adam are the bits of the same network
-        without it.  Independent of w3_first_wgrad.  Default False; setting it True while w3_step_path is off raises
-        DCLLUnsupported and leaves it off; w3_step_path = False clears it; switching it off is always allowed."""
-        return all(s.w3_dv for s in self.dcll_slices)
-
-    @w3_dv_path.setter
-    def w3_dv_path(self, on):
-        on = bool(on)
-        if on and not self.w3_step_path:
-            raise ops._lib.DCLLUnsupported('w3_dv_path needs w3_step_path (set it first)')
-        for s in self.dcll_slices:              # (part of _graph_signature: a captured timestep of the other path is retaken)
-            s.w3_dv = on
-
-    @property
-    def pool_dv_path(self):
-        """True: every learning step makes its backward call through dcll_conv_lif_backward_ex[_open] with DCLL_BWD_POOL_DV — the path
-        is the one the learning-path switches select — so a layer that pools takes its dv plane from k_bwd_dv_pool (a streaming form
-        of k_bwd_dv: a thread owns a pooled window) where ops.bwd_dv_pool_supported holds; a layer without pooling, or an unserved
-        one, keeps its kernel.  The plane is bit-identical, so every gradient and the parameters after Adam are the bits of the same
-        network without it.  Combines with every learning path and every step path except w3_step_path (which has w3_dv_path):
-        setting it True under w3_step_path raises DCLLUnsupported and leaves it off, and so does w3_step_path = True under it.
-        Default False; switching it off is always allowed."""
-        return all(s.pool_dv for s in self.dcll_slices)
-
-    @pool_dv_path.setter
-    def pool_dv_path(self, on):
-        on = bool(on)
-        if on and any(s.w3_learning_path for s in self.dcll_slices):
-            raise ops._lib.DCLLUnsupported('pool_dv_path cannot be combined with w3_step_path (w3_dv_path is its dv kernel)')
-        for s in self.dcll_slices:              # (part of _graph_signature: a captured timestep of the other path is retaken)
-            s.pool_dv = on
-
-    @property
-    def native_optim_path(self):
-        """True: the native learning step also serves slices whose optimizer is torch.optim.SGD, Adamax, AdamW, or Adam / AdamW with
-        amsgrad (DCLLBase.native_optimizers): their update is applied by k_grad_reduce_optim / k_optim_multi on the state tensors of
-        the torch optimizer objects, as torch's _single_tensor_* functions state it, instead of the whole step running under
-        autograd.  A network of plain Adam slices keeps its calls and its bits.  Combines with every learning, per-step and dv
-        path.  Default False (DCLL_NATIVE_OPTIM=1 sets it at construction); setting it True where a slice's optimizer is none of
-        DCLLBase.NATIVE_OPTIMIZERS, or uses maximize / capturable / fused / differentiable / a tensor lr or weight_decay, raises
-        DCLLUnsupported and leaves it as it was; switching it off is always allowed."""
-        return all(s.native_optimizers for s in self.dcll_slices)
-
-    @native_optim_path.setter
-    def native_optim_path(self, on):
-        on = bool(on)
-        if on:
-            for s in self.dcll_slices:
-                for o in ([getattr(s, 'optimizer', None)] + ([getattr(s, 'optimizer2', None)] if s.dclllayer.output_layer else [])):
-                    if o is None or not s._optimizer_served(o, True):
-                        raise ops._lib.DCLLUnsupported('native_optim_path: the optimizer of slice %s (%s) is not served'
-                                                       % (s.name, type(o).__name__))
-        for s in self.dcll_slices:              # (_native_learning looks at it again; _graph_signature follows the tensors' kinds)
-            s.native_optimizers = on
+    def _optimizer_not_served(self):
+        """'the optimizer of slice <name> (<class>)' of the first optimizer native_optim_path does not serve, None if it serves all"""
+        for s in self.dcll_slices:
+            for o in ([getattr(s, 'optimizer', None)] + ([getattr(s, 'optimizer2', None)] if s.dclllayer.output_layer else [])):
+                if o is None or not s._optimizer_served(o, True):
+                    return 'the optimizer of slice %s (%s)' % (s.name, type(o).__name__)
 
     # -- the fused path of any plain conv network (k_lif_seq_any, ABI 8): opt-in, beside test_sequence ---------------------
     def sequence_any_supported(self, wide=False, bands=None, tiles=None, slabs=None):
@@ -1379,3 +1057,7 @@ class ConvNetwork(torch.nn.Module):
             res['vote'].append(vote)
             cur = spk
         return res
+
+
+for _p in paths.PATHS:
+    setattr(ConvNetwork, _p.name, paths.network_property(_p))

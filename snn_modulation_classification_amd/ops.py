@@ -9,7 +9,7 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, paths
 from ._lib import ACT_NONE, ACT_SIGMOID, ConvDesc, DenseDesc, IQTail, LayerOpts, check, ptr, stream_ptr
 
 
@@ -112,7 +112,7 @@ def _check_layer_operands(desc, W, b, eps0, eps1, arp, B, tau=None, tau4=None):
 
 def conv_lif_step(desc, x, W, b, alpha, tau_m, alphas, tau_s, eps0, eps1, arp, i2o_W=None, i2o_b=None,
                   out_W=None, out_b=None, want_v=True, out=None, q8=None, stacked=None, finish=None, defer_ro=False,
-                  any_path=False, w3_path=False, wide_path=False, slab_path=False, bands=0):
+                  path=None, bands=0, any_path=False, w3_path=False, wide_path=False, slab_path=False):
     """One Conv2dDCLLlayer.forward step (dcll/pytorch_libdcll.py:599-608); state tensors are updated in place.
 
     Returns (s_pooled, p, o, pv_pooled, v) — p / o are None when the corresponding weights are None.
@@ -127,33 +127,25 @@ def conv_lif_step(desc, x, W, b, alpha, tau_m, alphas, tau_s, eps0, eps1, arp, i
     `defer_ro` (needs `finish`): where the fused readout tail serves the shape, only the layer kernel is launched now; the
     readout tail is left in finish['run_readouts'] for the caller to launch later (p / o are unwritten until then) — a
     learning timestep launches all layer kernels first (layer l+1 needs layer l's spikes, not its readouts).
-    `any_path`: the layer kernel is dcll_conv_lif_step_any — k_lif_step_any, one fp32-MFMA launch with the traces and the pooling
-    fused in, for any plain conv layer with c_out <= 32 and a kernel up to 16x16 (step_any_supported) — instead of
-    dcll_conv_lif_step's dispatch; the readout tails are the same.  fp32 weights only: with `q8` it raises.
-    `w3_path`: the layer kernel is dcll_conv_lif_step_w3 — k_lif_step_w3, one launch with the traces, the fp32-MFMA chains and the
-    (1,2) pooling fused in, for the (1,3)-kernel / 64-channel layers of radio_ml_conv_ref.yaml (step_w3_supported); the readout
-    tails are the same.  fp32 weights only; combined with `any_path` or `q8` it raises.
-    `wide_path`: the layer kernel is dcll_conv_lif_step_wide — k_lif_step_wide, k_lif_step_any's form with two 32-row M tiles, for
-    a plain conv layer with up to 64 output channels (step_wide_supported); a layer with c_out <= 32 runs the `any_path`
-    kernels, same bits and launch log.  fp32 weights only; combined with `q8`, `any_path` or `w3_path` it raises.
-    `slab_path`: the layer kernel is dcll_conv_lif_step_slab — k_lif_step_slab, k_lif_step_wide's chains over B x bands x slabs
-    workgroups (a band of output rows, a slab of 64 output channels each), for a plain conv layer of any number of output channels
-    and any plane height (step_slab_supported); `bands`: 0 = the plan's rule, N >= 1 = exactly N bands.  A layer `wide_path`
-    serves, with bands = 0, runs the `wide_path` kernels, same bits and launch log.  fp32 weights only; combined with `q8`,
-    `any_path`, `w3_path` or `wide_path` it raises.
+    `path` (ContinuousConv2D.step_path; paths.STEP_CALLS): the layer kernel instead of dcll_conv_lif_step's dispatch; the readout tails
+    are the same.  Every path reads fp32 weights only: with `q8` it raises.
+    'any': dcll_conv_lif_step_any — k_lif_step_any, one fp32-MFMA launch with the traces and the pooling fused in, for any plain conv
+    layer with c_out <= 32 and a kernel up to 16x16 (step_any_supported).
+    'w3': dcll_conv_lif_step_w3 — k_lif_step_w3, one launch with the traces, the fp32-MFMA chains and the (1,2) pooling fused in, for
+    the (1,3)-kernel / 64-channel layers of radio_ml_conv_ref.yaml (step_w3_supported).
+    'wide': dcll_conv_lif_step_wide — k_lif_step_wide, k_lif_step_any's form with two 32-row M tiles, for a plain conv layer with up to
+    64 output channels (step_wide_supported); a layer with c_out <= 32 runs the 'any' kernels, same bits and launch log.
+    'slab': dcll_conv_lif_step_slab — k_lif_step_slab, k_lif_step_wide's chains over B x bands x slabs workgroups (a band of output
+    rows, a slab of 64 output channels each), for a plain conv layer of any number of output channels and any plane height
+    (step_slab_supported); `bands` (with 'slab' only): 0 = the plan's rule, N >= 1 = exactly N bands.  A layer 'wide' serves, with
+    bands = 0, runs the 'wide' kernels, same bits and launch log.
+    The old keywords any_path / w3_path / wide_path / slab_path = True stand for path = 'any' / 'w3' / 'wide' / 'slab' (legacy_path).
     """
-    if slab_path and (q8 is not None or any_path or w3_path or wide_path):
-        raise ValueError("conv_lif_step(slab_path=True) cannot be combined with q8, any_path=True, w3_path=True or wide_path=True "
-                         "(fp32 weights, one layer kernel)")
-    if bands and not slab_path:
-        raise ValueError("conv_lif_step(bands=N) is an argument of slab_path=True")
-    if wide_path and (q8 is not None or any_path or w3_path):
-        raise ValueError("conv_lif_step(wide_path=True) cannot be combined with q8, any_path=True or w3_path=True (fp32 weights, "
-                         "one layer kernel)")
-    if any_path and q8 is not None:
-        raise ValueError("conv_lif_step(any_path=True) reads fp32 weights only (no q8)")
-    if w3_path and (any_path or q8 is not None):
-        raise ValueError("conv_lif_step(w3_path=True) cannot be combined with any_path=True or q8 (fp32 weights, one layer kernel)")
+    if any_path or w3_path or wide_path or slab_path or bands:
+        path, bands = legacy_path("step", path, bands, any_path=any_path, w3_path=w3_path, wide_path=wide_path, slab_path=slab_path)
+    if path is not None and q8 is not None:
+        raise ValueError("conv_lif_step(path=%r) reads fp32 weights only (no q8)" % path)
+    fn, w_query, tail_names = paths.STEP_CALLS[path]
     out = {} if out is None else out
     B = x.shape[0]
     ch, cw, ph, pw = conv_out_shape(desc)
@@ -182,20 +174,14 @@ def conv_lif_step(desc, x, W, b, alpha, tau_m, alphas, tau_s, eps0, eps1, arp, i
     v = buf('v', (B, desc.c_out, ch, cw), want_v)
     p = buf('p', (B, desc.target), i2o_W is not None)
     o = buf('o', (B, desc.target), bool(desc.output_layer))
-    scratch = buf('scratch', (2, B, desc.c_out, ch, cw), pooled and not any_path and not w3_path and not wide_path and not slab_path)
-    w_scratch = buf('w_scratch', (max(step_any_scratch(desc), 1),), True) if any_path else None       # (not served: the call refuses)
-    if wide_path:
-        w_scratch = buf('w_scratch', (max(step_wide_scratch(desc), 1),), True)
-    if slab_path:
-        w_scratch = buf('w_scratch', (max(step_slab_scratch(desc), 1),), True)
+    scratch = buf('scratch', (2, B, desc.c_out, ch, cw), pooled and path is None)
+    # (a layer the path does not serve: one float, the call itself then refuses)
+    w_scratch = buf('w_scratch', (max(int(getattr(_lib.get(), w_query)(ctypes.byref(desc))), 1),)) if w_query else None
+    args = dict(scratch=ptr(scratch), opts=opts, w_scratch=ptr(w_scratch), bands=int(bands))
+    tail = tuple(args[k] for k in tail_names)
 
     def layer_step(d, *readout_args):
-        """the layer call of this step: dcll_conv_lif_step, dcll_conv_lif_step_any / _wide (w_scratch for scratch, no opts),
-        dcll_conv_lif_step_slab (w_scratch and the band count) or dcll_conv_lif_step_w3 (neither)"""
-        fn = ("dcll_conv_lif_step_w3" if w3_path else "dcll_conv_lif_step_any" if any_path else
-              "dcll_conv_lif_step_wide" if wide_path else "dcll_conv_lif_step_slab" if slab_path else "dcll_conv_lif_step")
-        tail = (() if w3_path else (ptr(w_scratch),) if any_path or wide_path else (ptr(w_scratch), int(bands)) if slab_path
-                else (ptr(scratch), opts))
+        """the layer call of this step: dcll_conv_lif_step, or the path's with its own arguments behind `v` (paths.STEP_CALLS)"""
         rc = getattr(_lib.get(), fn)(
             ctypes.byref(d), ptr(x), ptr(W), ptr(b), ptr(alpha), ptr(tau_m), ptr(alphas), ptr(tau_s),
             ptr(eps0), ptr(eps1), ptr(arp), *readout_args, ptr(pv), ptr(v), *tail, B, stream_ptr())
@@ -396,55 +382,88 @@ BWD_W3F_PB = 128                # pixels of a job of k_bwd_wgrad_w3f (the flatte
 W3_FIRST_WGRAD, W3_DV = 1, 2    # flag bits of dcll_conv_lif_backward_w3_ex[_open] (DCLL_W3_FIRST_WGRAD, DCLL_W3_DV)
 
 
+def legacy_path(where, path=None, bands=0, w3_first=False, w3_dv=False, pool_dv=False, **legacy):
+    """The path of a conv_lif_step (`where` = "step") or conv_lif_backward ("backward") call -> (path, bands), from `path=` or the old
+    boolean keywords (paths.LEGACY_KEYWORDS: any_path, w3_path, wide_path, slab_path, and band_path of the backward).  ValueError for
+    what no call can be: two paths at once, a band count without its path ('slab' of the step, 'band' of the backward), w3_first or
+    w3_dv without the 'w3' path, pool_dv with it (w3_dv is that path's dv kernel).  Nothing has been called by then."""
+    chosen = {paths.LEGACY_KEYWORDS[k] for k, on in legacy.items() if on} | ({path} if path is not None else set())
+    if len(chosen) > 1:
+        raise ValueError("conv_lif_%s: the paths %s cannot be combined (one layer kernel per call)" % (where, " / ".join(sorted(chosen))))
+    path = chosen.pop() if chosen else None
+    if bands and path != ("slab" if where == "step" else "band"):
+        raise ValueError("conv_lif_%s(bands=N) is an argument of the %s path" % (where, "'slab'" if where == "step" else "'band'"))
+    if (w3_first or w3_dv) and path != "w3":
+        raise ValueError("conv_lif_backward(w3_first / w3_dv = True) needs the 'w3' path")
+    if pool_dv and path == "w3":
+        raise ValueError("conv_lif_backward(pool_dv=True) cannot be combined with the 'w3' path (w3_dv is that path's dv kernel)")
+    return path, bands
+
+
+def backward_entry(path, w3_first=False, w3_dv=False, pool_dv=False):
+    """The entry point of a conv_lif_backward call on `path` (its _open form: + "_open"): the path's own (paths.BACKWARD_CALLS), of the
+    'w3' path its w3f form with w3_first and its flag-word form with w3_dv, and the path / flag-word form of all others with pool_dv"""
+    if pool_dv:
+        return "dcll_conv_lif_backward_ex"
+    return "dcll_conv_lif_backward_w3_ex" if w3_dv else "dcll_conv_lif_backward_w3f" if w3_first else paths.BACKWARD_CALLS[path][0]
+
+
+def _jobs_chunks(desc, B, bands):
+    """one partial row per workgroup, up to 256 (a sample of a large plane is many 16x16 tile jobs, so small batches still fill the
+    chip); first layer: 128-thread workgroups, 6 KB partial rows"""
+    return min(B * max(1, (desc.h // 16) * (desc.w // 16)), 1024 if desc.c_in == 1 else 256)
+
+
+# partial rows of the weight gradient by the rule paths.BACKWARD_CALLS names
+_BWD_CHUNKS = {
+    'jobs': _jobs_chunks,
+    'batch': lambda desc, B, bands: min(B, BWD_ANY_MAX_CHUNKS),
+    # (a refused layer: one row, the call itself then raises with the library's message)
+    'plan': lambda desc, B, bands: backward_bands_plan(desc, B, bands)["nchunk"] if backward_bands_supported(desc, bands) else 1,
+    # (k_bwd_wgrad_w3: one row per 128-pixel block; the c_in 1 layer is the generic kernel's)
+    'w3': lambda desc, B, bands: (min(-(-B * desc.h * desc.w // 128), BWD_ANY_MAX_CHUNKS) if desc.c_in == 64
+                                  else _jobs_chunks(desc, B, bands)),
+}
+
+
 def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want_out, out=None, open_reduce=False, defer=None,
-                      any_path=False, w3_path=False, w3_first=False, w3_dv=False, wide_path=False, slab_path=False,
-                      band_path=False, bands=0, pool_dv=False):
+                      path=None, bands=0, w3_first=False, w3_dv=False, pool_dv=False, any_path=False, w3_path=False, wide_path=False,
+                      slab_path=False, band_path=False):
     """Gradients of one layer step (dcll_conv_lif_backward) -> (dW, db, d_outW, d_outb).  `out`: optional dict with
     preallocated 'dW', 'db', 'd_outW', 'd_outb', 'bwd_scratch' (the learning loop writes into the parameters' .grad).
     `open_reduce`: dcll_conv_lif_backward_open — dW / db are NOT written yet; the partial rows of the weight gradient stay
     in out['bwd_scratch'] and out['parts'] describes them for grad_reduce_adam, which finishes several layers in one launch.
     `defer` (a list; open form): nothing is launched — the prepared call is appended for conv_lif_backward_open_multi.
-    `any_path`: dcll_conv_lif_backward_any[_open] — the weight gradient on k_bwd_wgrad_any (fp32 MFMA, any plain conv layer with
-    c_out <= 32 and a kernel up to 16x16; backward_any_supported).  With `defer` the single open call is launched at once (there
-    is no multi-layer form of it) and nothing is appended.
-    `w3_path`: dcll_conv_lif_backward_w3[_open] — the weight gradient of a 64 -> 64 layer of the (1,3) / (1,2)-pool geometry on
-    k_bwd_wgrad_w3 (fp32 MFMA; backward_w3_supported); `defer` as for `any_path`; combined with `any_path` it raises.
-    `w3_first` (with `w3_path`; alone it raises): dcll_conv_lif_backward_w3f[_open] — the same, and the first layer of that geometry
+    `path` (DCLLBase.learning_path; paths.BACKWARD_CALLS): where the weight gradient comes from instead of the default dispatch.  With
+    `defer` the single open call of a path is launched at once (there is no multi-layer form of it) and nothing is appended.
+    'any': dcll_conv_lif_backward_any[_open] — k_bwd_wgrad_any (fp32 MFMA, any plain conv layer with c_out <= 32 and a kernel up to
+    16x16; backward_any_supported).
+    'w3': dcll_conv_lif_backward_w3[_open] — the weight gradient of a 64 -> 64 layer of the (1,3) / (1,2)-pool geometry on
+    k_bwd_wgrad_w3 (fp32 MFMA; backward_w3_supported).
+    `w3_first` (with 'w3'; alone it raises): dcll_conv_lif_backward_w3f[_open] — the same, and the first layer of that geometry
     (c_in 1) takes its weight gradient from k_bwd_wgrad_w3f (a streaming reduction) instead of the generic k_bwd_wgrad.
-    `w3_dv` (with `w3_path`; alone it raises; independent of `w3_first`): dcll_conv_lif_backward_w3_ex[_open] with DCLL_W3_DV — the
+    `w3_dv` (with 'w3'; alone it raises; independent of `w3_first`): dcll_conv_lif_backward_w3_ex[_open] with DCLL_W3_DV — the
     dv plane from k_bwd_dv_w3 instead of k_bwd_dv, bit for bit the same plane (a layer with more than 32 readout rows keeps
     k_bwd_dv); the scratch size is unchanged.
-    `wide_path`: dcll_conv_lif_backward_wide[_open] — the weight gradient of a plain conv layer with up to 64 output channels on
-    k_bwd_wgrad_wide (fp32 MFMA, two 32-row M tiles; backward_wide_supported); a layer with c_out <= 32 runs the `any_path` kernels,
-    same bits and launch log.  `defer` as for `any_path`; combined with `any_path` or `w3_path` it raises.
-    `slab_path`: dcll_conv_lif_backward_slab[_open] — the weight gradient of a plain conv layer of ANY width on k_bwd_wgrad_slab (fp32
-    MFMA, one slab of 64 output channels per workgroup; backward_slab_supported); a layer with c_out <= 64 runs the `wide_path`
-    kernels, same bits and launch log.  `defer` as for `any_path`; combined with any other path it raises.
-    `band_path`: dcll_conv_lif_backward_bands[_open] — the weight gradient of a plain conv layer of any width on a plane of ANY height
-    on k_bwd_wgrad_band (fp32 MFMA, a sample in bands of conv-output rows; backward_bands_supported).  `bands` (with `band_path`;
-    alone it raises): 0 the library's rule — a layer the `slab_path` serves runs that path, same bits and launch log —, 1 the
-    `slab_path` call itself, N >= 2 exactly N bands.  The partial-row scratch is sized from backward_bands_plan's nchunk.  `defer` as
-    for `any_path`; combined with any other path it raises.
+    'wide': dcll_conv_lif_backward_wide[_open] — the weight gradient of a plain conv layer with up to 64 output channels on
+    k_bwd_wgrad_wide (fp32 MFMA, two 32-row M tiles; backward_wide_supported); a layer with c_out <= 32 runs the 'any' kernels,
+    same bits and launch log.
+    'slab': dcll_conv_lif_backward_slab[_open] — the weight gradient of a plain conv layer of ANY width on k_bwd_wgrad_slab (fp32
+    MFMA, one slab of 64 output channels per workgroup; backward_slab_supported); a layer with c_out <= 64 runs the 'wide'
+    kernels, same bits and launch log.
+    'band': dcll_conv_lif_backward_bands[_open] — the weight gradient of a plain conv layer of any width on a plane of ANY height
+    on k_bwd_wgrad_band (fp32 MFMA, a sample in bands of conv-output rows; backward_bands_supported).  `bands` (with 'band';
+    alone it raises): 0 the library's rule — a layer the 'slab' path serves runs that path, same bits and launch log —, 1 the
+    'slab' call itself, N >= 2 exactly N bands.  The partial-row scratch is sized from backward_bands_plan's nchunk.
     `pool_dv`: the call goes through dcll_conv_lif_backward_ex[_open] with DCLL_BWD_POOL_DV and the path the other arguments select —
     the dv plane of a layer that pools from k_bwd_dv_pool instead of k_bwd_dv where bwd_dv_pool_supported holds, bit for bit the same
     plane; an unserved layer is unchanged, and for a layer without pooling the call is made exactly as without `pool_dv`; the scratch
-    size is unchanged.  With `defer` the slice's own open call is launched at once, as for `any_path`.  Combined with `w3_path` it raises (that path has `w3_dv`)."""
-    if pool_dv and w3_path:
-        raise ValueError("conv_lif_backward(pool_dv=True) cannot be combined with w3_path=True (w3_dv is that path's dv kernel)")
-    if band_path and (any_path or w3_path or wide_path or slab_path):
-        raise ValueError("conv_lif_backward(band_path=True) cannot be combined with any_path=True, w3_path=True, wide_path=True or slab_path=True")
-    if bands and not band_path:
-        raise ValueError("conv_lif_backward(bands=N) needs band_path=True")
-    if slab_path and (any_path or w3_path or wide_path):
-        raise ValueError("conv_lif_backward(slab_path=True) cannot be combined with any_path=True, w3_path=True or wide_path=True")
-    if wide_path and (any_path or w3_path):
-        raise ValueError("conv_lif_backward(wide_path=True) cannot be combined with any_path=True or w3_path=True")
-    if w3_path and any_path:
-        raise ValueError("conv_lif_backward(w3_path=True) cannot be combined with any_path=True")
-    if w3_first and not w3_path:
-        raise ValueError("conv_lif_backward(w3_first=True) needs w3_path=True")
-    if w3_dv and not w3_path:
-        raise ValueError("conv_lif_backward(w3_dv=True) needs w3_path=True")
+    size is unchanged.  With `defer` the slice's own open call is launched at once, as for a path.  Combined with 'w3' it raises (that
+    path has `w3_dv`).
+    The old keywords any_path / w3_path / wide_path / slab_path / band_path = True stand for `path` (legacy_path)."""
+    if any_path or w3_path or wide_path or slab_path or band_path or bands or w3_first or w3_dv or pool_dv:
+        path, bands = legacy_path("backward", path, bands, w3_first, w3_dv, pool_dv, any_path=any_path, w3_path=w3_path,
+                                  wide_path=wide_path, slab_path=slab_path, band_path=band_path)
     B = eps1.shape[0]
     dev = eps1.device
     out = {} if out is None else out
@@ -463,17 +482,11 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
     db = buf('db', (desc.c_out,))
     d_outW = buf('d_outW', (desc.target, K), want_out)
     d_outb = buf('d_outb', (desc.target,), want_out)
-    # partial-sum rows for the weight gradient: one per workgroup, up to 256 (a sample of a large plane is many 16x16
-    # tile jobs, so small batches still fill the chip); the same area then holds the batch chunks of the output_ gradient
-    jobs = B * max(1, (desc.h // 16) * (desc.w // 16))
+    # partial-sum rows for the weight gradient, one per workgroup (_BWD_CHUNKS); the same area then holds the batch chunks of the
+    # output_ gradient
+    _, ex_path, chunk_rule = paths.BACKWARD_CALLS[path]
     per_chunk = desc.c_out * ((desc.c_in // desc.groups) * desc.kh * desc.kw + 1)
-    nchunk = min(jobs, 1024 if desc.c_in == 1 else 256)      # (first layer: 128-thread workgroups, 6 KB partial rows)
-    if any_path or wide_path or slab_path:
-        nchunk = min(B, BWD_ANY_MAX_CHUNKS)
-    if band_path:       # (a refused layer: one row, the call itself then raises with the library's message)
-        nchunk = backward_bands_plan(desc, B, bands)["nchunk"] if backward_bands_supported(desc, bands) else 1
-    if w3_path and desc.c_in == 64:
-        nchunk = min(-(-B * desc.h * desc.w // 128), BWD_ANY_MAX_CHUNKS)       # (k_bwd_wgrad_w3: one row per 128-pixel block)
+    nchunk = _BWD_CHUNKS[chunk_rule](desc, B, bands)
     if w3_first and desc.c_in == 1:
         nchunk = min(-(-B * desc.h * desc.w // BWD_W3F_PB), BWD_ANY_MAX_CHUNKS)  # (k_bwd_wgrad_w3f: one row per job)
     part = nchunk * per_chunk
@@ -490,24 +503,13 @@ def conv_lif_backward(desc, eps1, v, pv_pooled, g_p, g_o, g_pv, g_v, i2o_W, want
     # allocator as soon as ptr() returns, and the NEXT temporary's copy can be given the same block (two expanded stride-0
     # gradients in one call would then alias)
     gp_, go_, gpv_, gv_ = c(g_p), (c(g_o) if want_out else None), c(g_pv), c(g_v)
-    fn = "dcll_conv_lif_backward_w3f" if w3_first else "dcll_conv_lif_backward_w3" if w3_path else "dcll_conv_lif_backward_any" if any_path else "dcll_conv_lif_backward"
-    if wide_path:
-        fn = "dcll_conv_lif_backward_wide"
-    if slab_path:
-        fn = "dcll_conv_lif_backward_slab"
-    if band_path:
-        fn = "dcll_conv_lif_backward_bands"
-    band_arg = (int(bands),) if band_path else ()
-    flags = ()
-    if w3_dv:       # (the flag-word entry points; without w3_dv the calls above are made as before)
-        fn, flags = "dcll_conv_lif_backward_w3_ex", (W3_DV | (W3_FIRST_WGRAD if w3_first else 0),)
     if pool_dv and desc.pool_h == 1 and desc.pool_w == 1:
         pool_dv = False     # (a layer without pooling: the flag changes nothing, so the call — its multi-layer form included — is made as before)
-    if pool_dv:     # (the path / flag-word entry points; without pool_dv the calls above are made as before)
-        path = (BWD_PATH_BANDS if band_path else BWD_PATH_SLAB if slab_path else BWD_PATH_WIDE if wide_path else
-                BWD_PATH_ANY if any_path else BWD_PATH_DEFAULT)
-        fn, band_arg, flags = "dcll_conv_lif_backward_ex", (), (path, int(bands), BWD_POOL_DV)
-    if defer is not None and not any_path and not w3_path and not wide_path and not slab_path and not band_path and not pool_dv:       # (open form, launched later with other layers': conv_lif_backward_open_multi)
+    fn = backward_entry(path, w3_first, w3_dv, pool_dv)
+    band_arg = (int(bands),) if path == 'band' and not pool_dv else ()
+    # (the flag-word entry points; without w3_dv / pool_dv the calls are made as before them)
+    flags = (ex_path, int(bands), BWD_POOL_DV) if pool_dv else (W3_DV | (W3_FIRST_WGRAD if w3_first else 0),) if w3_dv else ()
+    if defer is not None and path is None and not pool_dv:       # (open form, launched later with other layers': conv_lif_backward_open_multi)
         item = _lib.BwdItem(ctypes.pointer(desc), ptr(eps1), ptr(v), ptr(pv_pooled), ptr(gp_), ptr(go_), ptr(gpv_), ptr(gv_),
                             ptr(i2o_W), ptr(d_outW), ptr(d_outb), ptr(scratch), n_scratch, B, 0, None, 0, 0)
         defer.append(dict(item=item, out=out, desc=desc, dW=dW, db=db, scratch=scratch,

@@ -491,7 +491,7 @@ def test_entry_point_train_mnist_with_any_learning_path(tmp_path, capsys, monkey
     real = ops.conv_lif_backward
 
     def counted(*a, **kw):
-        calls.append(bool(kw.get("any_path", False)))
+        calls.append(bool(kw.get("any_path", False)) or kw.get("path") == "any")           # (the old keyword, or path=)
         return real(*a, **kw)
     monkeypatch.setattr(ops, "conv_lif_backward", counted)
     common = ['--data', 'MNIST', '--network_spec', os.path.join(PKG, 'networks', 'mnist_conv.yaml'), '--synthetic', '16',

@@ -643,7 +643,8 @@ def test_entry_point_train_with_band_learning_path(tmp_path, capsys, monkeypatch
     real = ops.conv_lif_backward
 
     def counted(*a, **kw):
-        calls.append((bool(kw.get("band_path", False)), int(kw.get("bands", 0)), bool(kw.get("slab_path", False))))
+        calls.append((bool(kw.get("band_path", False)) or kw.get("path") == "band", int(kw.get("bands", 0)),
+                      bool(kw.get("slab_path", False)) or kw.get("path") == "slab"))          # (the old keywords, or path=)
         return real(*a, **kw)
     monkeypatch.setattr(ops, "conv_lif_backward", counted)
     common = ['--arp', '1.0', '--burnin', '4', '--batch_size', '4', '--batch_size_test', '4', '--n_test_samples', '4', '--synthetic', '8',

@@ -578,7 +578,8 @@ def test_entry_point_train_mnist_with_slab_learning_path(tmp_path, capsys, monke
     real = ops.conv_lif_backward
 
     def counted(*a, **kw):
-        calls.append((bool(kw.get("slab_path", False)), bool(kw.get("wide_path", False))))
+        calls.append((bool(kw.get("slab_path", False)) or kw.get("path") == "slab",
+                      bool(kw.get("wide_path", False)) or kw.get("path") == "wide"))          # (the old keywords, or path=)
         return real(*a, **kw)
     monkeypatch.setattr(ops, "conv_lif_backward", counted)
     common = ['--data', 'MNIST', '--network_spec', os.path.join(PKG, 'networks', 'mnist_conv.yaml'), '--synthetic', '16',

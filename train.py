@@ -285,16 +285,7 @@ def main(argv=None):
         print('-' * 80)
     net = net.to(pytorch_libdcll.device)
     net.reset(True)
-    _opt_in_any_learning(net, args)
-    _opt_in_any_step(net, args)
-    _opt_in_w3_step(net, args)
-    _opt_in_wide_step(net, args)
-    _opt_in_slab_step(net, args)
-    _opt_in_wide_learning(net, args)
-    _opt_in_slab_learning(net, args)
-    _opt_in_band_learning(net, args)
-    _opt_in_pool_dv(net, args)
-    _opt_in_native_optim(net, args)
+    _opt_in_paths(net, args)
     parallel.freeze_startup_heap()          # (a full GC pass over the start-up heap costs ~100 ms inside the T-loop)
 
     if not args.no_save:
@@ -327,18 +318,10 @@ def main(argv=None):
     import time
     t_train, n_train = 0.0, 0
 
-    # --any_sequence_path: a network without a specialised sequence kernel is tested on k_lif_seq_any (one process only; several
-    # ranks keep evaluate_batch's sharded per-step evaluation)
-    use_any = args.any_sequence_path and not use_sequence and world == 1 and net.sequence_any_supported()
-    # --wide_sequence_path: the same with wide=True (layers of up to 64 output channels: a --netscale up to 2)
-    use_wide = _opt_in_wide_sequence(net, args, use_sequence, world)
-    # --band_sequence_path [N]: the same through dcll_conv_lif_sequence_bands; wins over the two above
-    use_bands = _opt_in_band_sequence(net, args, use_sequence, world)
-    # --tile_sequence_path [TY TX]: the same through dcll_conv_lif_sequence_tiles; wins over the three above
-    use_tiles = _opt_in_tile_sequence(net, args, use_sequence, world)
-    # --slab_sequence_path [TY TX]: the same through dcll_conv_lif_sequence_slabs (any number of output channels); wins over the four above
-    use_slabs = _opt_in_slab_sequence(net, args, use_sequence, world)
-    use_any = use_any or use_wide or use_bands is not None or use_tiles is not None or use_slabs is not None
+    # --any_sequence_path / --wide_sequence_path / --band_sequence_path [N] / --tile_sequence_path [TY TX] / --slab_sequence_path [TY TX]: a
+    # network without a specialised sequence kernel is tested on ConvNetwork.test_sequence_any (one process only; several ranks keep
+    # evaluate_batch's sharded per-step evaluation)
+    seq_any = _opt_in_sequence(net, args, use_sequence, world)
 
     def evaluate_batch_any(samples, labels1h):
         """The per-step branch of evaluate_batch (host-encoded planes, reference test_radio_ml.py:142-146) with its T-loop replaced
@@ -349,15 +332,14 @@ def main(argv=None):
                                         max_Q=args.Q_bounds[1], max_duration=T)
         net.reset()
         net.eval()
-        net.test_sequence_any(torch.Tensor(spikes).to(pytorch_libdcll.device)[:T], wide=use_wide, bands=use_bands,
-                              tiles=use_tiles, slabs=use_slabs)
+        net.test_sequence_any(torch.Tensor(spikes).to(pytorch_libdcll.device)[:T], **seq_any)
         return net.accuracy(torch.as_tensor(np.asarray(targets), dtype=torch.float32))
 
     def run_tests(step):
         net.batch_size = max(1, np.diff(parallel.shard_range(args.batch_size_test, rank, world))[0])
         acc = np.empty([len(test_batches), len(net.dcll_slices)])
         for i, (samples, labels) in enumerate(test_batches):
-            if use_any:
+            if seq_any is not None:
                 acc[i, :] = evaluate_batch_any(samples, to_one_hot(labels, target_size))
                 continue
             acc[i, :], _ = evaluation.evaluate_batch(net, args, samples, to_one_hot(labels, target_size), encoder,
@@ -450,246 +432,72 @@ def main(argv=None):
     return out_dir
 
 
-def _opt_in_wide_sequence(net, args, use_sequence, world=1):
-    """--wide_sequence_path: True where the test phase runs ConvNetwork.test_sequence_any(wide=True) — the caller's test phase
-    does not run the specialised sequence kernels (use_sequence False), one process, every layer served by
-    dcll_conv_lif_sequence_wide; elsewhere a notice and the default path."""
-    if not args.wide_sequence_path:
-        return False
-    if use_sequence:
-        why = 'the network runs its geometry-specialised sequence kernels'
-    elif world > 1:
-        why = 'several ranks keep the sharded per-step evaluation'
-    elif not net.sequence_any_supported(wide=True):
-        why = 'dcll_conv_lif_sequence_wide does not serve every layer of this network'
-    else:
-        return True
-    print('--wide_sequence_path ignored: ' + why)
-    return False
-
-
-def _opt_in_band_sequence(net, args, use_sequence, world=1):
-    """--band_sequence_path [N]: the band count (0: the library's rule) where the test phase runs
-    ConvNetwork.test_sequence_any(bands=N) — the conditions of --wide_sequence_path with dcll_conv_lif_sequence_bands' predicate;
-    None elsewhere, with a notice where the flag was given."""
-    bands = getattr(args, 'band_sequence_path', None)
-    if bands is None:
-        return None
-    if use_sequence:
-        why = 'the network runs its geometry-specialised sequence kernels'
-    elif world > 1:
-        why = 'several ranks keep the sharded per-step evaluation'
-    elif bands < 0 or not net.sequence_any_supported(bands=bands):
-        why = 'dcll_conv_lif_sequence_bands does not serve every layer of this network with %s' % (
-            '%d bands' % bands if bands else 'any band count')
-    else:
-        return bands
-    print('--band_sequence_path ignored: ' + why)
-    return None
-
-
-def _tile_sequence_arg(args):
-    """--tile_sequence_path [TY TX] -> (ty, tx), None where the flag is absent (both omitted: (0, 0))"""
-    t = getattr(args, 'tile_sequence_path', None)
+def _tile_sequence_arg(args, flag='tile_sequence_path'):
+    """--tile_sequence_path / --slab_sequence_path [TY TX] -> (ty, tx), None where the flag is absent (both omitted: (0, 0))"""
+    t = getattr(args, flag, None)
     if t is None:
         return None
     if len(t) not in (0, 2):
-        raise SystemExit('--tile_sequence_path takes no value or two (TY TX)')
+        raise SystemExit('--%s takes no value or two (TY TX)' % flag)
     return (int(t[0]), int(t[1])) if t else (0, 0)
 
 
-def _opt_in_tile_sequence(net, args, use_sequence, world=1):
-    """--tile_sequence_path [TY TX]: the tile plan ((0, 0): the library's rule) where the test phase runs
-    ConvNetwork.test_sequence_any(tiles=(TY, TX)) — the conditions of --band_sequence_path with dcll_conv_lif_sequence_tiles'
-    predicate; None elsewhere, with a notice where the flag was given."""
-    tiles = _tile_sequence_arg(args)
-    if tiles is None:
-        return None
-    if use_sequence:
-        why = 'the network runs its geometry-specialised sequence kernels'
-    elif world > 1:
-        why = 'several ranks keep the sharded per-step evaluation'
-    elif min(tiles) < 0 or not net.sequence_any_supported(tiles=tiles):
-        why = 'dcll_conv_lif_sequence_tiles does not serve every layer of this network with %s' % (
-            '%d x %d tiles' % tiles if tiles != (0, 0) else 'any tile plan')
-    else:
-        return tiles
-    print('--tile_sequence_path ignored: ' + why)
-    return None
+def _opt_in_sequence(net, args, use_sequence, world=1):
+    """The keyword arguments of ConvNetwork.test_sequence_any for the test phase, None where it does not run there.  It runs where a
+    sequence flag is given, the caller's test phase does not run the specialised sequence kernels (use_sequence False), there is one
+    process, and the flag's call serves every layer.  --slab_sequence_path [TY TX] (dcll_conv_lif_sequence_slabs) wins over
+    --tile_sequence_path [TY TX] (..._tiles) over --band_sequence_path [N] (..._bands) over --wide_sequence_path (..._wide) over
+    --any_sequence_path; every flag that was given and is not the one served prints a notice, --any_sequence_path keeps silent."""
+    plan = lambda t: '%d x %d tiles' % t if t != (0, 0) else 'any tile plan'
+    bands = getattr(args, 'band_sequence_path', None)
+    # flag, test_sequence_any's keyword, its value (None: not given), whether the value is valid, how a notice words the value
+    flags = [('slab', 'slabs', _tile_sequence_arg(args, 'slab_sequence_path'), lambda t: min(t) >= 0, plan),
+             ('tile', 'tiles', _tile_sequence_arg(args), lambda t: min(t) >= 0, plan),
+             ('band', 'bands', bands, lambda n: n >= 0, lambda n: '%d bands' % n if n else 'any band count'),
+             ('wide', 'wide', True if args.wide_sequence_path else None, lambda v: True, None)]
+    chosen = None
+    for flag, kw, value, valid, words in flags:
+        if value is None:
+            continue
+        if use_sequence:
+            why = 'the network runs its geometry-specialised sequence kernels'
+        elif world > 1:
+            why = 'several ranks keep the sharded per-step evaluation'
+        elif not valid(value) or not net.sequence_any_supported(**{kw: value}):
+            why = 'dcll_conv_lif_sequence_%s does not serve every layer of this network' % kw + (' with ' + words(value) if words else '')
+        else:
+            chosen = chosen or {kw: value}
+            continue
+        print('--%s_sequence_path ignored: %s' % (flag, why))
+    if chosen is None and args.any_sequence_path and not use_sequence and world == 1 and net.sequence_any_supported():
+        chosen = {}
+    return chosen
 
 
-def _opt_in_slab_sequence(net, args, use_sequence, world=1):
-    """--slab_sequence_path [TY TX]: the tile plan per (sample, slab) ((0, 0): the library's rule) where the test phase runs
-    ConvNetwork.test_sequence_any(slabs=(TY, TX)) — the conditions of --tile_sequence_path with dcll_conv_lif_sequence_slabs'
-    predicate; None elsewhere, with a notice where the flag was given."""
-    t = getattr(args, 'slab_sequence_path', None)
-    if t is None:
-        return None
-    if len(t) not in (0, 2):
-        raise SystemExit('--slab_sequence_path takes no value or two (TY TX)')
-    slabs = (int(t[0]), int(t[1])) if t else (0, 0)
-    if use_sequence:
-        why = 'the network runs its geometry-specialised sequence kernels'
-    elif world > 1:
-        why = 'several ranks keep the sharded per-step evaluation'
-    elif min(slabs) < 0 or not net.sequence_any_supported(slabs=slabs):
-        why = 'dcll_conv_lif_sequence_slabs does not serve every layer of this network with %s' % (
-            '%d x %d tiles' % slabs if slabs != (0, 0) else 'any tile plan')
-    else:
-        return slabs
-    print('--slab_sequence_path ignored: ' + why)
-    return None
-
-
-def _opt_in_any_learning(net, args):
-    """--any_learning_path: switch the network's learning step to k_bwd_wgrad_any where every slice is served."""
-    if not args.any_learning_path:
-        return
-    if net.backward_any_supported():
-        net.any_learning_path = True
-    else:
-        print('--any_learning_path ignored: k_bwd_wgrad_any does not serve every layer of this network')
-
-
-def _opt_in_wide_learning(net, args):
-    """--wide_learning_path: switch the network's learning step to dcll_conv_lif_backward_wide (k_bwd_wgrad_wide for layers of 33-64
-    output channels, k_bwd_wgrad_any below) where every slice is served and no other learning path is in effect."""
-    if not getattr(args, 'wide_learning_path', False):
-        return
-    if net.any_learning_path or net.w3_step_path:
-        print('--wide_learning_path ignored: another learning path (--any_learning_path / --w3_step_path) is in effect')
-    elif net.backward_wide_supported():
-        net.wide_learning_path = True
-    else:
-        print('--wide_learning_path ignored: dcll_conv_lif_backward_wide does not serve every layer of this network')
-
-
-def _opt_in_slab_learning(net, args):
-    """--slab_learning_path: switch the network's learning step to dcll_conv_lif_backward_slab (k_bwd_wgrad_slab for layers of more
-    than 64 output channels, the wide path's kernels below) where every slice is served and no other learning path is in effect."""
-    if not getattr(args, 'slab_learning_path', False):
-        return
-    if net.any_learning_path or net.wide_learning_path or net.w3_step_path:
-        print('--slab_learning_path ignored: another learning path (--any_learning_path / --wide_learning_path / --w3_step_path) '
-              'is in effect')
-    elif net.backward_slab_supported():
-        net.slab_learning_path = True
-    else:
-        print('--slab_learning_path ignored: dcll_conv_lif_backward_slab does not serve every layer of this network')
-
-
-def _opt_in_band_learning(net, args):
-    """--band_learning_path [N]: switch the network's learning step to dcll_conv_lif_backward_bands (k_bwd_wgrad_band where a sample
-    does not fit a workgroup's LDS, the slab path's kernels where it does) where every slice is served and no other learning path
-    is in effect."""
-    n = getattr(args, 'band_learning_path', None)
-    if n is None:
-        return
-    if net.any_learning_path or net.wide_learning_path or net.slab_learning_path or net.w3_step_path:
-        print('--band_learning_path ignored: another learning path (--any_learning_path / --wide_learning_path / '
-              '--slab_learning_path / --w3_step_path) is in effect')
-    elif n < 0:
-        print('--band_learning_path ignored: a band count is >= 0')
-    elif net.backward_bands_supported(n):
-        net.band_learning_path = n if n else True
-    else:
-        print('--band_learning_path ignored: dcll_conv_lif_backward_bands does not serve every layer of this network' +
-              (' with %d bands' % n if n else ''))
-
-
-def _opt_in_any_step(net, args):
-    """--any_step_path: switch the network's per-step layer calls to k_lif_step_any where every layer is served."""
-    if not args.any_step_path:
-        return
-    if net.step_any_supported():
-        net.any_step_path = True
-    else:
-        print('--any_step_path ignored: k_lif_step_any does not serve every layer of this network')
-
-
-def _opt_in_wide_step(net, args):
-    """--wide_step_path: switch the network's per-step layer calls to dcll_conv_lif_step_wide (k_lif_step_wide for layers of 33-64
-    output channels, k_lif_step_any below) where every layer is served and no other per-step path is in effect."""
-    if not getattr(args, 'wide_step_path', False):
-        return
-    if net.any_step_path or net.w3_step_path:
-        print('--wide_step_path ignored: another per-step path (--any_step_path / --w3_step_path) is in effect')
-    elif net.step_wide_supported():
-        net.wide_step_path = True
-    else:
-        print('--wide_step_path ignored: k_lif_step_wide does not serve every layer of this network')
-
-
-def _opt_in_slab_step(net, args):
-    """--slab_step_path: switch the network's per-step layer calls to dcll_conv_lif_step_slab (k_lif_step_slab for layers of more
-    than 64 output channels or planes beyond a workgroup's LDS, dcll_conv_lif_step_wide's kernels below) where every layer is
-    served and no other per-step path is in effect."""
-    if not getattr(args, 'slab_step_path', False):
-        return
-    if net.any_step_path or net.w3_step_path or net.wide_step_path:
-        print('--slab_step_path ignored: another per-step path (--any_step_path / --wide_step_path / --w3_step_path) is in effect')
-    elif net.step_slab_supported():
-        net.slab_step_path = True
-    else:
-        print('--slab_step_path ignored: k_lif_step_slab does not serve every layer of this network')
-
-
-def _opt_in_w3_step(net, args):
-    """--w3_step_path: switch the network's per-step layer calls and weight gradients to k_lif_step_w3 / k_bwd_wgrad_w3 where
-    every layer is served; --w3_first_wgrad with it: the first layer's weight gradient on k_bwd_wgrad_w3f; --w3_dv_path with it:
-    every layer's dv plane from k_bwd_dv_w3."""
-    first, dv = getattr(args, 'w3_first_wgrad', False), getattr(args, 'w3_dv_path', False)
-    if not args.w3_step_path:
-        if first:
-            print('--w3_first_wgrad ignored: it rides on --w3_step_path, which is not given')
-        if dv:
-            print('--w3_dv_path ignored: it rides on --w3_step_path, which is not given')
-        return
-    if net.w3_step_supported():
-        net.w3_step_path = True
-        if first:
-            net.w3_first_wgrad = True
-        if dv:
-            net.w3_dv_path = True
-    else:
-        print('--w3_step_path ignored: k_lif_step_w3 / k_bwd_wgrad_w3 do not serve every layer of this network')
-        if first:
-            print('--w3_first_wgrad ignored: --w3_step_path is not in effect on this network')
-        if dv:
-            print('--w3_dv_path ignored: --w3_step_path is not in effect on this network')
-
-
-def _opt_in_pool_dv(net, args):
-    """--pool_dv_path: the learning step's backward calls through dcll_conv_lif_backward_ex with DCLL_BWD_POOL_DV (k_bwd_dv_pool for
-    the layers that pool); runs behind the other opt-ins, whose paths it keeps."""
-    if not getattr(args, 'pool_dv_path', False):
-        return
-    if net.w3_step_path:
-        print('--pool_dv_path ignored: --w3_step_path is in effect (its dv kernel is --w3_dv_path)')
-    elif not any(tuple(s.dclllayer.pooling) != (1, 1) for s in net.dcll_slices):
-        print('--pool_dv_path ignored: no layer of this network pools')
-    else:
-        net.pool_dv_path = True
-
-
-def _opt_in_native_optim(net, args):
-    """--native_optim_path: slices whose optimizer is SGD, Adamax, AdamW or uses amsgrad learn on the native step
-    (ConvNetwork.native_optim_path); runs behind the other opt-ins, whose paths it keeps."""
-    if not getattr(args, 'native_optim_path', False):
-        return
-    from snn_modulation_classification_amd._lib import DCLLUnsupported
-    if all(s._plain_adam() for s in net.dcll_slices):
-        print('--native_optim_path ignored: every optimizer of this network is plain Adam, which the native step serves already')
-        return
-    try:
-        net.native_optim_path = True
-    except DCLLUnsupported as e:
-        print('--native_optim_path ignored: %s' % e)
-        return
-    if not all(s._native_learning() is not None for s in net.dcll_slices):
-        net.native_optim_path = False
-        print('--native_optim_path ignored: the learning step of this network is not native whatever its optimizer (loss type, '
-              'layer options or DCLL_NATIVE_LEARNING=0 keep it under autograd)')
+def _opt_in_paths(net, args):
+    """The flags of the opt-in per-step and learning paths, in the order of paths.PATHS: `net.<switch> = <the flag's value>` where the
+    network accepts it, else a notice and the path as it was (paths.refusal: what it rides on, another path in effect, a layer that
+    is not served)."""
+    from snn_modulation_classification_amd import paths
+    for p in paths.PATHS:
+        v = getattr(args, p.name, None)
+        if v is None or v is False:
+            continue
+        v = True if p.key != 'band' or v == 0 else v          # (--band_learning_path [N]; 0 bands: the library's rule)
+        if p.name == 'pool_dv_path' and not any(tuple(s.dclllayer.pooling) != (1, 1) for s in net.dcll_slices) and not net.w3_step_path:
+            print('--pool_dv_path ignored: no layer of this network pools')
+        elif p.name == 'native_optim_path' and all(s._plain_adam() for s in net.dcll_slices):
+            print('--native_optim_path ignored: every optimizer of this network is plain Adam, which the native step serves already')
+        else:
+            why = paths.refusal(net, p, v)
+            if why:
+                print('--%s ignored: %s' % (p.name, paths.notice_text(p, why, v, given=bool(getattr(args, p.rides_on or '', False)))))
+                continue
+            setattr(net, p.name, v)
+            if p.name == 'native_optim_path' and not all(s._native_learning() is not None for s in net.dcll_slices):
+                net.native_optim_path = False
+                print('--native_optim_path ignored: the learning step of this network is not native whatever its optimizer (loss type, '
+                      'layer options or DCLL_NATIVE_LEARNING=0 keep it under autograd)')
 
 
 def main_mnist(args):
@@ -715,20 +523,8 @@ def main_mnist(args):
         print('Loaded the SNN model from `%s`.' % args.restore_path)
     net = net.to(pytorch_libdcll.device)
     net.reset(True)
-    _opt_in_any_learning(net, args)
-    _opt_in_any_step(net, args)
-    _opt_in_w3_step(net, args)
-    _opt_in_wide_step(net, args)
-    _opt_in_slab_step(net, args)
-    _opt_in_wide_learning(net, args)
-    _opt_in_slab_learning(net, args)
-    _opt_in_band_learning(net, args)
-    _opt_in_pool_dv(net, args)
-    _opt_in_native_optim(net, args)
-    use_wide = _opt_in_wide_sequence(net, args, net.sequence_supported())      # (the condition of --any_sequence_path below)
-    use_bands = _opt_in_band_sequence(net, args, net.sequence_supported())
-    use_tiles = _opt_in_tile_sequence(net, args, net.sequence_supported())
-    use_slabs = _opt_in_slab_sequence(net, args, net.sequence_supported())
+    _opt_in_paths(net, args)
+    seq_any = _opt_in_sequence(net, args, net.sequence_supported())
     parallel.freeze_startup_heap()          # (a full GC pass over the start-up heap costs ~100 ms inside the T-loop)
     n_test = int(np.ceil(float(args.n_test_samples) / args.batch_size_test))
     if args.synthetic:
@@ -780,16 +576,8 @@ def main_mnist(args):
                 tx, ty = spikes_of(ts, tl, st_test)
                 net.reset()
                 net.eval()
-                if use_slabs is not None:
-                    net.test_sequence_any(tx[:args.n_iters_test], slabs=use_slabs)
-                elif use_tiles is not None:
-                    net.test_sequence_any(tx[:args.n_iters_test], tiles=use_tiles)
-                elif use_bands is not None:
-                    net.test_sequence_any(tx[:args.n_iters_test], bands=use_bands)
-                elif use_wide:
-                    net.test_sequence_any(tx[:args.n_iters_test], wide=True)
-                elif args.any_sequence_path and not net.sequence_supported() and net.sequence_any_supported():
-                    net.test_sequence_any(tx[:args.n_iters_test])
+                if seq_any is not None:
+                    net.test_sequence_any(tx[:args.n_iters_test], **seq_any)
                 else:
                     for t in range(args.n_iters_test):
                         net.test(x=tx[t])
